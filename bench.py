@@ -16,8 +16,12 @@ The default warmup of 10 steps keeps the GPU clock ramp out of the timed window 
 warmups measured 0.85-0.89M rows/s on the same box that gives 1.03-1.07M after 10).
 rows/step/GPU = FF input rows + images.  Synthetic data, random-init weights, bf16 compute.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line. --dump-outputs DIR also writes what
+the last timed step computed (DIR/<name>.npy, float32; seeded samples of the two output sets). --full adds the
+untimed comparison with the fp32 reference (config.check in the result line).
 
 Without torchrun (WORLD_SIZE unset) and N > 1, bench.py launches its own ranks: N child processes, one per GPU
 (LOCAL_RANK = GPU index, RCCL; gloo on a CPU-only host), started as ordinary subprocesses BEFORE this process makes
@@ -68,6 +72,42 @@ def verify(client, cv, ff, w, b, dev, nrows=16, nimg=2, single_job=False):
             "conv_images": nimg, "conv_max_rel_err": conv_err, "ok": bool(ok)}
 
 
+DUMP_FF_ROWS = 256          # rows of the FF output kept by --dump-outputs (256 x 14588 fp32 = 15 MB at full size)
+DUMP_CONV_ELEMS = 1 << 21   # elements of the conv2d output kept by --dump-outputs (8 MB + 16 MB of float64 indices)
+
+
+def dump_outputs(client, out_dir, rank=0):
+    """Write what the last timed step left in the two output sets: the FF-NN 'output' set (softmax rows) and the
+    conv2d 'conv_out' set, as float32 .npy files. An output larger than its budget is sampled at fixed positions
+    (seeded generator, sorted indices into rows / the flattened array), so two runs with the same arguments write
+    the same positions; the indices are written next to the values (float64). About 40 MB at the full size."""
+    import numpy as np
+
+    from netsdb_amd.models.blocks import to_tensor
+
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    g = torch.Generator().manual_seed(20240229)
+
+    def save(name, t):
+        t = t.detach().cpu()
+        t = t.double() if t.dtype in (torch.int64, torch.float64) else t.float()   # indices stay exact in float64
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), t.contiguous().numpy())
+
+    out = to_tensor(client, "ff", "output", gather=False)
+    if out.shape[0] > DUMP_FF_ROWS:
+        rows = torch.randperm(out.shape[0], generator=g)[:DUMP_FF_ROWS].sort().values
+        save("ff_output_rows", rows)
+        out = out[rows.to(out.device)]
+    save("ff_output", out)
+    conv = client.storage.get_set("conv2d", "conv_out").all().columns["data"]
+    if conv.numel() > DUMP_CONV_ELEMS:
+        idx = torch.randint(0, conv.numel(), (DUMP_CONV_ELEMS,), generator=g).sort().values
+        save("conv_out_index", idx)
+        conv = conv.reshape(-1)[idx.to(conv.device)]
+    save("conv_out", conv)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -75,6 +115,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--small", action="store_true", help="tiny shapes (CPU smoke only; not a valid measurement)")
     ap.add_argument("--dropout", type=float, default=0.5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (FF 'output' set, conv2d "
+                         "'conv_out' set; seeded samples where large) as DIR/<name>.npy in float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed comparison of sampled FF rows "
+                         "and conv2d images with the fp32 reference (config.check in the result line)")
     ap.add_argument("--settle-ms", type=float, default=400.0,
                     help="untimed steps run before the W warmup steps until this much wall time has passed: "
                          "the chip's clock dips for ~10-20 ms after the GEMMs start and then settles "
@@ -185,7 +231,9 @@ def main():
     rows_local = local_rows + cfg["images"]
     rows_total = ctx.all_reduce_scalar(float(rows_local), "sum") * args.steps
     value = rows_total / dt
-    check = verify(client, cv, ff, w, b, dev, single_job=args.single_job)
+    if args.dump_outputs:
+        dump_outputs(client, args.dump_outputs, ctx.rank)
+    check = verify(client, cv, ff, w, b, dev, single_job=args.single_job) if args.full else None
     if ctx.rank == 0:
         res = {
             "metric": "inference rows/sec (whole node), FF-NN + conv2d block",
@@ -209,7 +257,7 @@ def main():
                 "seq_len": None,
                 "parallelism": f"dp{ctx.world_size} (row-partitioned inputs, broadcast model)",
                 "small": bool(args.small),
-                "check": check,
+                **({"check": check} if args.full else {}),
                 "settle_steps_untimed": settle_steps,
                 "conv_overlap": args.overlap,
                 "collectives_per_step": round(coll_per_step, 2),

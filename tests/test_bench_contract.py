@@ -22,8 +22,8 @@ def _last_json(out: str) -> dict:
                                    ["--single-job"]])
 def test_bench_single_process(extra):
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
-    r = subprocess.run([sys.executable, "bench.py", "--small", "--steps", "2", "--warmup", "2"] + extra, cwd=ROOT,
-                       env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, "bench.py", "--small", "--full", "--steps", "2", "--warmup", "2"] + extra,
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 1 and d["steps"] == 2 and d["value"] > 0
@@ -31,11 +31,34 @@ def test_bench_single_process(extra):
     assert d["config"]["check"]["ok"] is True and d["config"]["check"]["ff_max_rel_err"] < 1e-2
 
 
+def test_bench_plain_run_dumps_repeatable_outputs(tmp_path):
+    """A plain run (no ``--full``) skips the reference check; ``--dump-outputs`` writes the last timed step's two
+    output sets as float32/float64 arrays, and a second run with the same arguments writes the same values."""
+    import numpy as np
+
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    got = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--small", "--steps", "3", "--warmup", "1", "--dump-outputs",
+                            str(tmp_path / d)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = _last_json(r.stdout)
+        assert KEYS <= set(res) and res["steps"] == 3 and res["ms_per_step"] > 0 and "check" not in res["config"]
+        got.append({f: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))})
+    assert set(got[0]) == {"ff_output.npy", "conv_out.npy"}
+    assert got[0]["ff_output.npy"].shape == (64, 512) and got[0]["conv_out.npy"].shape == (4, 16, 26, 26)
+    np.testing.assert_allclose(got[0]["ff_output.npy"].sum(-1), 1.0, atol=1e-2)      # softmax rows, bf16 storage
+    for f, x in got[0].items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all()
+        assert np.array_equal(x, got[1][f]), f
+
+
 def test_bench_two_ranks_gloo():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29561", "bench.py", "--gpus", "2", "--small",
-                        "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+                        "--full", "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True,
+                       timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 2 * (64 + 4)
@@ -49,7 +72,7 @@ def test_bench_self_launches_ranks():
     """``bench.py --gpus 2`` without torchrun spawns its own two ranks (gloo on this CPU host) and reports n_gpus 2."""
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--small", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--small", "--full", "--steps", "2", "--warmup", "1"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)

@@ -66,7 +66,7 @@ def _samples():
     return out
 
 
-@pytest.mark.parametrize("name,program", _samples() or [("inline", "A = ones(20,20,2,2)\nB = identity(20,2)\nC = A + B")])
+@pytest.mark.parametrize("name,program", _samples() + [("inline", "A = ones(20,20,2,2)\nB = identity(20,2)\nC = A + B")])
 def test_reference_samples(tmp_path, name, program):
     c = PDBClient(root=str(tmp_path))
     la = LAInstance(c, dtype=torch.float32)
@@ -75,6 +75,41 @@ def test_reference_samples(tmp_path, name, program):
     for var, exp in ref.items():
         got = la.get(var).double().cpu()
         torch.testing.assert_close(got, exp, atol=1e-3, rtol=1e-3, msg=f"{name}:{var}")
+
+
+_M = "A = ones(5,5,3,3)\nI = identity(5,3)\nM = A + I\n"      # 15x15 in 3x3 blocks of 5x5: ones + identity
+
+# one program per operator of the DSL, kept in this file so that every operator is checked wherever the suite runs:
+# block shapes that are not square, more than one block per side
+OPERATOR_PROGRAMS = [
+    ("add", _M + "P = ones(4,6,3,2)\nQ = ones(4,6,3,2)\nC = P + Q"),
+    ("subtract", _M + "C = M - I\nD = I - M"),
+    ("hadamard", _M + "C = M * M\nD = (M + I) * (A - I)"),
+    ("transpose", _M + "P = ones(4,6,3,2)\nB = P^T\nC = (M - A)^T"),
+    ("inverse", _M + "B = M^-1\nC = I^-1"),
+    ("duplicate_row", "A = ones(1,6,1,4)\nB = duplicateRow(A,3,5)"),
+    ("duplicate_col", "A = ones(6,1,4,1)\nB = duplicateCol(A,3,5)"),
+    ("row_max", _M + "B = rowMax(M)"),
+    ("row_min", _M + "B = rowMin(M)"),
+    ("row_sum", _M + "B = rowSum(M)\nC = rowSum(ones(4,6,3,2))"),
+    ("col_max", _M + "B = colMax(M)"),
+    ("col_min", _M + "B = colMin(M)"),
+    ("col_sum", _M + "B = colSum(M)\nC = colSum(ones(4,6,3,2))"),
+    ("max", _M + "B = max(M)"),
+    ("min", _M + "B = min(M)"),
+    ("matmul", _M + "P = ones(4,6,3,2)\nQ = ones(6,5,2,3)\nC = P %*% Q\nD = M %*% M"),
+    ("transpose_multiply", _M + "P = ones(4,6,3,2)\nC = P '* P\nD = M '* I"),
+    ("gram_inverse", _M + "B = (M '* M)^-1"),
+]
+
+
+@pytest.mark.parametrize("name,program", OPERATOR_PROGRAMS, ids=[n for n, _ in OPERATOR_PROGRAMS])
+def test_operator_programs(tmp_path, name, program):
+    c = PDBClient(root=str(tmp_path))
+    la = LAInstance(c, dtype=torch.float32)
+    la.run(program)
+    for var, exp in ref_eval(program).items():
+        torch.testing.assert_close(la.get(var).double().cpu(), exp, atol=1e-3, rtol=1e-3, msg=f"{name}:{var}")
 
 
 def test_regression_program(tmp_path):
