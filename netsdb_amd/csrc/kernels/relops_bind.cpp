@@ -46,6 +46,10 @@ int nsdb_run_count(const void* keys, long long n, unsigned* cnt, long long* off,
 int nsdb_run_reduce(const void* keys, const void* vals, long long rs, long long cs, int F, int vt, int op, long long n,
                     const long long* off, long long G, long long* heads, long long* okey, void* oagg, long long* ocnt,
                     hipStream_t st);
+int nsdb_order_limit_max_k();
+long long nsdb_order_limit_state_bytes(const int* dt, int m, long long n);
+int nsdb_order_limit(const void* const* keys, const int* dt, const int* desc, int m, long long n, long long k,
+                     void* state, unsigned* lists, unsigned* win, long long* out, hipStream_t st);
 }
 
 namespace {
@@ -505,6 +509,46 @@ std::vector<torch::Tensor> take_many(std::vector<torch::Tensor> cols, torch::Ten
   flush();
   return out;
 }
+
+// ORDER BY keys[0], keys[1], ... LIMIT k (topk.hip): the int64 row ids of the min(k, n) first rows in final order;
+// desc[j]: key j orders descending; equal rows by ascending row id. Keys: 1..4 one-dimensional int32 / int64 /
+// float32 / float64 GPU columns of equal length n < 2^31 (read in place at their native width), min(k, n) <= 2048.
+// No host read: a linear chain of launches on the current stream, scratch from the caching allocator.
+torch::Tensor order_limit(std::vector<torch::Tensor> keys, std::vector<bool> desc, int64_t k) {
+  const int m = (int)keys.size();
+  TORCH_CHECK(m >= 1 && m <= 4, "order_limit: 1 to 4 key columns");
+  TORCH_CHECK((int)desc.size() == m, "order_limit: one direction per key");
+  const int64_t n = keys[0].numel();
+  const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+  int dt[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
+  for (int j = 0; j < m; ++j) {
+    auto& c = keys[j];
+    TORCH_CHECK(c.is_cuda() && c.dim() == 1 && c.numel() == n && c.device() == keys[0].device(),
+                "order_limit: keys must be 1-D GPU columns of equal length on one device");
+    const auto t = c.scalar_type();
+    dt[j] = t == torch::kInt32 ? 0 : t == torch::kFloat32 ? 1 : t == torch::kInt64 ? 2 : t == torch::kFloat64 ? 3 : -1;
+    TORCH_CHECK(dt[j] >= 0, "order_limit: keys must be int32, int64, float32 or float64");
+    c = c.contiguous();
+    ptr[j] = c.data_ptr();
+    ds[j] = desc[j] ? 1 : 0;
+  }
+  auto i64 = keys[0].options().dtype(torch::kInt64);
+  if (n == 0 || k <= 0) return torch::empty({0}, i64);
+  TORCH_CHECK(n < (int64_t(1) << 31), "order_limit: at most 2^31 - 1 rows");
+  const int64_t k_eff = std::min<int64_t>(k, n);
+  TORCH_CHECK(k_eff <= nsdb_order_limit_max_k(), "order_limit: k above ", nsdb_order_limit_max_k());
+  const int64_t sbytes = nsdb_order_limit_state_bytes(dt, m, n);
+  TORCH_CHECK(sbytes > 0, "order_limit: bad key set");
+  auto i32 = keys[0].options().dtype(torch::kInt32);
+  auto state = torch::zeros({(sbytes + 7) / 8}, i64);
+  auto lists = torch::empty({2 * n}, i32);
+  auto win = torch::empty({k_eff}, i32);
+  auto out = torch::empty({k_eff}, i64);
+  rc_ok(nsdb_order_limit(ptr, dt, ds, m, n, k, state.data_ptr(), reinterpret_cast<unsigned*>(lists.data_ptr<int>()),
+                         reinterpret_cast<unsigned*>(win.data_ptr<int>()), LL(out.data_ptr<int64_t>()), stream()),
+        "order_limit");
+  return out;
+}
 }  // namespace
 
 std::vector<torch::Tensor> hash_aggregate_impl(torch::Tensor keys, c10::optional<torch::Tensor> vals,
@@ -542,6 +586,9 @@ void register_relops(pybind11::module& m) {
   m.def("run_aggregate", &run_aggregate, "group-by of keys arriving in runs: (reps, aggs, counts, first) or [] when "
         "the keys are not ordered", pybind11::arg("keys"), pybind11::arg("vals") = pybind11::none(),
         pybind11::arg("op") = "sum");
+  m.def("order_limit", &order_limit, "ORDER BY keys (desc[j]: key j descending; ties by row id) LIMIT k: int64 row ids "
+        "in final order, no host read", pybind11::arg("keys"), pybind11::arg("desc"), pybind11::arg("k"));
+  m.attr("ORDER_LIMIT_MAX_K") = nsdb_order_limit_max_k();
   m.def("mix64", &mix64, "key hash mix64((x ^ y) + GOLD) per row, one pass", pybind11::arg("x"),
         pybind11::arg("y") = pybind11::none());
 }

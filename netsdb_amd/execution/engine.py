@@ -998,9 +998,11 @@ class QueryEngine:
         return reps, agg
 
     def _topk(self, comp, batches, kcol, vcol, out_ts, out_col, state):
-        """TopKComp: per-rank top k by score on the device (torch.topk over the device score column; objects
-        gathered with a device take), then the ranks' candidates meet through one packed all-gather and the
-        global top k is selected on the device again. No host copy of the scores."""
+        """TopKComp: per-rank top k by score on the device (K.order_limit, topk.hip, over the device score column;
+        objects gathered with a device take), then the ranks' candidates meet through one packed all-gather and the
+        global top k is selected on the device again. No host copy of the scores; integer scores compare exactly;
+        rows tied at the k-th score are kept lowest row first (rank-major row order after the all-gather), so repeated
+        runs keep the same rows."""
         objs, scores = [], []
         for x in batches:
             objs.append(x.columns[kcol])
@@ -1011,17 +1013,14 @@ class QueryEngine:
             ob = column_concat(objs)
             dev = scores[0].device
             sc = torch.cat([s.to(dev) for s in scores])
-            if not sc.is_floating_point():
-                sc = sc.double()
-            k = min(comp.k, sc.numel())
-            top = torch.topk(sc, k).indices
-            local = RecordBatch({"o": column_take(ob, top), "s": sc.index_select(0, top)}, k)
+            top = K.order_limit([sc], comp.k, descending=True, stats=self.pipeline_stats)
+            local = RecordBatch({"o": column_take(ob, top), "s": sc.index_select(0, top)}, int(top.numel()))
         if self.ctx.distributed:
             got = [g for g in self.ctx.broadcast_batch_all(local) if g is not None and g.n]
             local = RecordBatch.concat(got) if got else None
             if local is not None:
-                k = min(comp.k, local.n)
-                local = local.take(torch.topk(local.columns["s"], k).indices)
+                local = local.take(K.order_limit([local.columns["s"]], comp.k, descending=True,
+                                                 stats=self.pipeline_stats))
             if self.ctx.rank != 0:
                 local = None
         if local is None or local.n == 0:

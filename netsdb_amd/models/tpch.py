@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from ..computations import AggregateComp, JoinComp, ScanSet, SelectionComp, TopKComp, WriteSet
+from ..execution import kernels as K
 from ..lambdas import IsIn, KeyTuple, Like, Literal, Select, Values, make_batch_lambda, make_lambda_from_member
 from ..objects.record import PDBObject, RecordBatch
 from ..objects.strings import StringColumn, to_host, use_device_strings
@@ -567,11 +568,9 @@ def q03(client, db: str, segment: str = "BUILDING", date: int = 19950315, k: int
     r = _flat(_run(client, db, "q03_out", agg.set_input(j), "tpch_q03"))
     if r is None:
         return []
-    # top-k on the device (revenue desc, orderdate, orderkey): three stable sorts, only k rows reach the host
+    # ORDER BY revenue DESC, o_orderdate, l_orderkey LIMIT k on the device (K.order_limit): only k rows reach the host
     ok_, od, sp, rev = (torch.as_tensor(r.columns[c]) for c in ("k0", "k1", "k2", "revenue"))
-    order = torch.argsort(ok_, stable=True)
-    order = order[torch.argsort(od[order], stable=True)]
-    order = order[torch.argsort(-rev[order].double(), stable=True)][:k]
+    order = K.order_limit([rev, od, ok_], k, descending=[True, False, False], stats=client.engine.pipeline_stats)
     return [{"l_orderkey": int(a), "o_orderdate": int(b_), "o_shippriority": int(c), "revenue": float(v)}
             for a, b_, c, v in zip(ok_[order].tolist(), od[order].tolist(), sp[order].tolist(), rev[order].tolist())]
 
@@ -816,8 +815,8 @@ def q02(client, db: str, size: int = 15, type_suffix: str = "BRASS", region: str
     if isinstance(acct, torch.Tensor) and acct.numel() > k:
         # ORDER BY s_acctbal DESC, ... LIMIT k: only rows at or above the k-th balance can be in the answer (ties at
         # that balance are decided by the string keys below), so only those cross to the host and get decoded
-        a64 = acct.double()
-        b = b.take(torch.nonzero(a64 >= torch.topk(a64, k).values[-1]).flatten())
+        kth = acct[K.order_limit([acct], k, True, stats=client.engine.pipeline_stats)[-1]]
+        b = b.take(torch.nonzero(acct >= kth).flatten())
     hv = _lists({c: b.columns[c] for c in ("s_acctbal", "s_name", "n_name", "p_partkey", "p_mfgr")})
     rows = [{"s_acctbal": float(a), "s_name": s, "n_name": n, "p_partkey": int(p), "p_mfgr": m}
             for a, s, n, p, m in zip(hv["s_acctbal"], hv["s_name"], hv["n_name"], hv["p_partkey"], hv["p_mfgr"])]

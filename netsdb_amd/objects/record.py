@@ -482,6 +482,13 @@ class RecordBatch:
             cols[k] = column_take(c, idx)
         return RecordBatch(cols, n, self.type)
 
+    def order_limit(self, cols: Sequence[str], k: int, descending=False) -> "RecordBatch":
+        """ORDER BY the named (numeric tensor) columns LIMIT k: the first ``min(k, n)`` rows in final order
+        (execution.kernels.order_limit: ``descending`` one bool or one per column, ties by row id)."""
+        from ..execution import kernels as K
+
+        return self.take(K.order_limit([self.columns[c] for c in cols], k, descending))
+
     def slice(self, s: int, e: int) -> "RecordBatch":
         cols = {k: column_slice(c, s, e) for k, c in self.columns.items()}
         return RecordBatch(cols, max(0, min(e, self.n) - s), self.type)

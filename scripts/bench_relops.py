@@ -4,9 +4,12 @@
     hash_aggregate (relops.hip) vs torch.unique(return_inverse) + index_add_;
   * hash join: build 2 M rows, probe 16 M rows (PK-FK, ~1 match per probe) via JoinTable vs sort + searchsorted;
     and a build-size sweep (2 / 16 / 64 M unique build keys, 16 M probes): build, probe, build + probe;
-  * partition permutation of 16 M rows over 8 destinations: partition_perm vs argsort(stable) + bincount.
+  * partition permutation of 16 M rows over 8 destinations: partition_perm vs argsort(stable) + bincount;
+  * ORDER BY ... LIMIT k (K.order_limit, topk.hip) at --rows: one float64 key descending, k = 10 / 100 / 2048, vs
+    torch.topk + a sort of the k values; three keys (float64 descending, int32, int64), k = 10, vs the chain of three
+    stable argsorts.
 
-    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json]
+    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json] [--sections order_limit]
 """
 import argparse
 import json
@@ -38,7 +41,49 @@ def run(fns, rounds):
     for _ in range(rounds):
         for k, f in fns.items():
             res[k].append(wall(f))
-    return {k: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4)} for k, v in res.items()}
+    return {k: {"ms_median": round(statistics.median(v), 4), "ms_min": round(min(v), 4), "ms_max": round(max(v), 4)}
+            for k, v in res.items()}
+
+
+def bench_order_limit(a, out):
+    """K.order_limit against the torch composites it replaces, both arms alternating in the same rounds."""
+    dev = "cuda:0"
+    n = a.rows
+    g = torch.Generator(device=dev).manual_seed(1)
+    out["order_limit"] = {}
+    x = torch.rand(n, device=dev, dtype=torch.float64, generator=g)
+    for k in (10, 100, 2048):
+        def dev_ol():
+            return K.order_limit([x], k, True)
+
+        def torch_topk_sort():
+            v, i = torch.topk(x, min(k, n), sorted=False)
+            return i[torch.sort(v, descending=True, stable=True).indices]
+
+        assert torch.equal(x[dev_ol()], x[torch_topk_sort()]), "order_limit differs from torch.topk"
+        t = run({"order_limit": dev_ol, "torch_topk_sort": torch_topk_sort}, a.rounds)
+        t["keys"], t["k"] = "f64 desc", k
+        out["order_limit"][f"1key_k{k}"] = t
+        print(json.dumps({"order_limit": f"1key_k{k}", **t}), flush=True)
+    # three keys: about 16 rows share each value of key 0, so keys 1 and 2 decide inside its groups
+    rev = torch.floor(x * (n / 16)) / (n / 16)
+    od = torch.randint(0, 2500, (n,), device=dev, generator=g, dtype=torch.int32)
+    ok = torch.randint(0, 1 << 40, (n,), device=dev, generator=g, dtype=torch.int64)
+    del x
+
+    def dev_ol3():
+        return K.order_limit([rev, od, ok], 10, [True, False, False])
+
+    def torch_argsort3():
+        order = torch.argsort(ok, stable=True)
+        order = order[torch.argsort(od[order], stable=True)]
+        return order[torch.argsort(rev[order], descending=True, stable=True)][:10]
+
+    assert torch.equal(dev_ol3(), torch_argsort3()), "order_limit differs from the argsort chain"
+    t = run({"order_limit": dev_ol3, "torch_argsort_chain": torch_argsort3}, a.rounds)
+    t["keys"], t["k"] = "f64 desc, i32, i64", 10
+    out["order_limit"]["3key_k10"] = t
+    print(json.dumps({"order_limit": "3key_k10", **t}), flush=True)
 
 
 def main():
@@ -46,12 +91,25 @@ def main():
     ap.add_argument("--rows", type=int, default=16_000_000)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--sections", default="all", help="all, or order_limit alone (the other sections run together)")
     a = ap.parse_args()
+    out = {"rows": a.rows}
+    if a.sections != "order_limit":
+        bench_tables(a, out)
+    bench_order_limit(a, out)
+    if a.json:
+        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+def bench_tables(a, out):
+    """The group-by, join and partition sections."""
     dev = "cuda:0"
     n = a.rows
     g = torch.Generator(device=dev).manual_seed(0)
     h = _ext.hip()
-    out = {"rows": n, "groupby": {}, "join": {}, "partition": {}}
+    out.update({"groupby": {}, "join": {}, "partition": {}})
     vals = torch.rand(n, device=dev, dtype=torch.float64, generator=g)
     for distinct in (8, 1000, 3000, 5000, 10_000, 10_000_000):
         keys = torch.randint(0, distinct, (n,), device=dev, generator=g) * 2654435761
@@ -157,10 +215,6 @@ def main():
                                                 torch.bincount(dest, minlength=8).tolist())}, a.rounds)
     out["partition"] = t
     print(json.dumps({"partition": t}), flush=True)
-    if a.json:
-        os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
 
 
 if __name__ == "__main__":
