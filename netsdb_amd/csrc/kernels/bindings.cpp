@@ -105,6 +105,12 @@ void check_cuda(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
 }
 
+// An optional operand's pointer goes to the same launch as `ref`'s: it must live on ref's device (a CPU tensor
+// would hand the kernel a host pointer).
+void check_same_device(const torch::Tensor& t, const torch::Tensor& ref, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), name, " must be a GPU tensor on the device of the main operand");
+}
+
 bool is_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == torch::kFloat32 || t.scalar_type() == torch::kBFloat16, name,
               " must be float32 or bfloat16");
@@ -423,9 +429,12 @@ torch::Tensor softmax_rows(torch::Tensor X, c10::optional<torch::Tensor> bias, b
   TORCH_CHECK(X.dim() == 2 && X.stride(-1) == 1, "X must be 2-D row-contiguous");
   const bool xf = is_f32(X, "X");
   const float* bptr = nullptr;
+  torch::Tensor b;   // dense copy of a strided bias view; alive until the launch
   if (bias.has_value() && bias->defined()) {
+    check_same_device(*bias, X, "bias");
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->numel() == X.size(1), "bias f32[N]");
-    bptr = bias->data_ptr<float>();
+    b = bias->contiguous();
+    bptr = b.data_ptr<float>();
   }
   auto Y = torch::empty({X.size(0), X.size(1)}, X.options().dtype(out_f32 ? torch::kFloat32 : torch::kBFloat16));
   check_rc(nsdb_softmax_rows(X.data_ptr(), xf, bptr, Y.data_ptr(), out_f32, (int)X.size(0), (int)X.size(1),
@@ -440,10 +449,13 @@ torch::Tensor bias_act(torch::Tensor X, c10::optional<torch::Tensor> bias, int64
   TORCH_CHECK(X.dim() == 2 && X.is_contiguous(), "X must be contiguous 2-D");
   const bool xf = is_f32(X, "X");
   const float* bptr = nullptr;
+  torch::Tensor b;   // dense copy of a strided bias view; alive until the launch
   if (bias.has_value() && bias->defined()) {
+    check_same_device(*bias, X, "bias");
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32, "bias f32");
     TORCH_CHECK(bias->numel() == (bias_mode == 1 ? X.size(0) : X.size(1)), "bias length mismatch");
-    bptr = bias->data_ptr<float>();
+    b = bias->contiguous();
+    bptr = b.data_ptr<float>();
   }
   auto Y = torch::empty_like(X, X.options().dtype(out_f32 ? torch::kFloat32 : torch::kBFloat16));
   check_rc(nsdb_bias_act(X.data_ptr(), xf, bptr, Y.data_ptr(), out_f32, (int)X.size(0), (int)X.size(1),
@@ -459,6 +471,7 @@ std::vector<torch::Tensor> lstm_cell(torch::Tensor gates, c10::optional<torch::T
   const int64_t B = gates.size(0), H = gates.size(1) / 4;
   const float* cp = nullptr;
   if (c_prev.has_value() && c_prev->defined()) {
+    check_same_device(*c_prev, gates, "c_prev");
     TORCH_CHECK(c_prev->scalar_type() == torch::kFloat32 && c_prev->numel() == B * H && c_prev->is_contiguous(),
                 "c_prev f32 [B,H]");
     cp = c_prev->data_ptr<float>();
@@ -501,13 +514,18 @@ torch::Tensor embedding_bag(torch::Tensor table, torch::Tensor idx, torch::Tenso
   check_cuda(table, "table");
   TORCH_CHECK(table.dim() == 2 && table.is_contiguous(), "table [V,D] contiguous");
   const bool tf = is_f32(table, "table");
+  check_same_device(idx, table, "idx");
+  check_same_device(offsets, table, "offsets");
   TORCH_CHECK(idx.scalar_type() == torch::kInt64 && offsets.scalar_type() == torch::kInt64, "int64 idx/offsets");
   TORCH_CHECK(idx.is_contiguous() && offsets.is_contiguous() && offsets.dim() == 1 && offsets.numel() >= 1,
               "idx/offsets contiguous");
   const float* wp = nullptr;
+  torch::Tensor w;   // dense copy of a strided weights view (the kernel reads weights[i]); alive until the launch
   if (weights.has_value() && weights->defined()) {
+    check_same_device(*weights, table, "weights");
     TORCH_CHECK(weights->scalar_type() == torch::kFloat32 && weights->numel() == idx.numel(), "weights f32[nnz]");
-    wp = weights->data_ptr<float>();
+    w = weights->contiguous();
+    wp = w.data_ptr<float>();
   }
   const int64_t Bn = offsets.numel() - 1, D = table.size(1);
   auto out = torch::empty({Bn, D}, table.options().dtype(torch::kFloat32));

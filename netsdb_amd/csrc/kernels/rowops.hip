@@ -40,11 +40,14 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(const TI* X, const fl
   float m = -INFINITY, s = 0.f;
   for (int j = threadIdx.x; j < N; j += blockDim.x) {
     const float v = ld(x, j) + (bias ? bias[j] : 0.f);
+    // a -inf element (masked logit) adds nothing and is never subtracted from m: -inf - -inf is NaN. v > m rules
+    // out v == -inf; a NaN element is not > m and not -inf, so it reaches __expf and poisons s (the row is NaN).
     if (v > m) { s = s * __expf(m - v) + 1.f; m = v; }
-    else s += __expf(v - m);
+    else if (v != -INFINITY) s += __expf(v - m);
   }
   const float gm = block_reduce(m, red, true);
-  s = (m == -INFINITY) ? 0.f : s * __expf(m - gm);
+  // a thread that saw no finite element keeps its s (0, or NaN after a NaN element): no m - gm for it
+  if (m != -INFINITY) s *= __expf(m - gm);
   const float gs = block_reduce(s, red, false);
   const float inv = 1.f / gs, lgs = logf(gs);
   TO* y = Y + (long long)row * ldy;
