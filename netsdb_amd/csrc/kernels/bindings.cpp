@@ -32,6 +32,8 @@ struct ConvOpts {
 int nsdb_conv2d_igemm(const void* X, const void* Wt, const float* bias, void* out, int N, int C, int H, int W,
                       int OC, int KH, int KW, int stride, int pad, int dil, int ldw, int act, int nchw_out,
                       int out_f32, const void* wfrag, const struct ConvOpts* opts, hipStream_t stream);
+int nsdb_conv2d_plan(int N, int C, int H, int W, int OC, int KH, int KW, int stride, int pad, int dil, int ldw,
+                     int nchw_out, int out_f32, int has_wfrag, const struct ConvOpts* opts);
 int nsdb_prefetch(const void* ptr, long long bytes, unsigned* sink, int blocks, hipStream_t stream);
 int nsdb_im2col(const void* X, void* out, int N, int C, int H, int W, int KH, int KW, int stride, int pad, int dil,
                 int ldk, hipStream_t stream);
@@ -393,6 +395,21 @@ torch::Tensor conv2d(torch::Tensor X, torch::Tensor Wt, c10::optional<torch::Ten
                              nchw_out ? 1 : 0, out_f32 ? 1 : 0, fptr, &o, cur_stream()),
            "conv2d");
   return out;
+}
+
+// The kernel nsdb_conv2d_igemm would launch for this geometry and these options (host arithmetic only, no tensors).
+std::string conv2d_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t OC, int64_t KH, int64_t KW, int64_t stride,
+                        int64_t pad, int64_t dil, int64_t ldw, bool nchw_out, bool out_f32, bool has_wfrag,
+                        int64_t kernel, int64_t max_blocks, bool force_generic, int64_t variant, int64_t contig) {
+  TORCH_CHECK(stride >= 1 && dil >= 1 && pad >= 0, "bad conv geometry");
+  const ConvOpts o{force_generic ? 1 : 0, (int)variant, max_blocks < 0 ? 512 : (int)max_blocks, kernel < 0 ? 5 : (int)kernel,
+                   (int)contig};
+  const int plan = nsdb_conv2d_plan((int)N, (int)C, (int)H, (int)W, (int)OC, (int)KH, (int)KW, (int)stride, (int)pad,
+                                    (int)dil, (int)ldw, nchw_out ? 1 : 0, out_f32 ? 1 : 0, has_wfrag ? 1 : 0, &o);
+  check_rc(plan < 0 ? plan : 0, "conv2d_plan");
+  static const char* const names[] = {"igemm", "rows", "rows_staged", "rowfull", "ws", "diag"};
+  TORCH_CHECK(plan < 6, "conv2d_plan: unknown plan ", plan);
+  return names[plan];
 }
 
 torch::Tensor im2col(torch::Tensor X, int64_t KH, int64_t KW, int64_t stride, int64_t pad, int64_t dil, int64_t ldk) {
@@ -791,6 +808,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d", &conv2d, py::arg("X"), py::arg("W"), py::arg("bias") = py::none(), py::arg("KH") = 1,
         py::arg("KW") = 1, py::arg("stride") = 1, py::arg("pad") = 0, py::arg("dil") = 1, py::arg("act") = 0,
         py::arg("nchw_out") = false, py::arg("out_f32") = false, py::arg("wfrag") = py::none(), py::arg("kernel") = -1,
+        py::arg("max_blocks") = -1, py::arg("force_generic") = false, py::arg("variant") = 0, py::arg("contig") = 0);
+  m.def("conv2d_plan", &conv2d_plan, py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("OC"),
+        py::arg("KH"), py::arg("KW"), py::arg("stride") = 1, py::arg("pad") = 0, py::arg("dil") = 1, py::arg("ldw") = 0,
+        py::arg("nchw_out") = false, py::arg("out_f32") = false, py::arg("has_wfrag") = false, py::arg("kernel") = -1,
         py::arg("max_blocks") = -1, py::arg("force_generic") = false, py::arg("variant") = 0, py::arg("contig") = 0);
   m.def("im2col", &im2col);
   m.def("softmax_rows", &softmax_rows, py::arg("X"), py::arg("bias") = py::none(), py::arg("out_f32") = true,

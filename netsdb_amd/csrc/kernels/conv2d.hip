@@ -1141,112 +1141,139 @@ struct ConvOpts {
   int contig;          // full-row kernel: contiguous row-group runs per block (A/B)
 };
 
+// Which kernel a call gets (nsdb_conv2d_plan / ops.conv2d_plan report it, nsdb_conv2d_igemm launches it).
+enum {
+  NSDB_CONV_IGEMM = 0,        // conv2d_igemm_kernel (any geometry)
+  NSDB_CONV_ROWS = 1,         // conv2d_rows_kernel, direct stores
+  NSDB_CONV_ROWS_STAGED = 2,  // conv2d_rows_kernel, LDS-staged bf16 NCHW output
+  NSDB_CONV_ROWFULL = 3,      // conv2d_rowfull_kernel
+  NSDB_CONV_WS = 4,           // conv2d_ws_kernel
+  NSDB_CONV_DIAG = 5          // a timing build (kernel 2/3/4/6 or variant != 0): the output is not the convolution
+};
+
+// The dispatcher: pure host arithmetic on the call's geometry and options, no tensors and no launch. Returns the
+// plan (>= 0) or the call's error (-1 bad filter layout / empty output, -2 image too large for the 31-bit byte
+// offsets of the buffer loads). ``out_align8``: the output pointer is 8-B aligned. A row plan fills the geometry
+// fields of *q (when given); pointers, act and variant are the launcher's.
+static int conv_plan(int N, int C, int H, int W, int OC, int KH, int KW, int stride, int pad, int dil, int ldw,
+                     int nchw_out, int out_f32, int has_wfrag, int out_align8, const ConvOpts& o,
+                     nsdb::ConvRowParams* q_out) {
+  const int OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+  const int OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+  const int K = C * KH * KW;
+  if (ldw % 8 != 0 || ldw < K || OH <= 0 || OW <= 0) return -1;
+  // Every kernel masks a load by giving it the byte offset 0x7ffffff0 and relies on the buffer range check to
+  // return 0: the image must end below that offset (this also keeps the kernels' 32-bit byte offsets exact).
+  if ((long long)N * C * H * W * 2 >= 0x7ffffff0LL) return -2;
+  // row-tiled LDS kernel for small-C, wide-row layers (see conv2d_rows_kernel)
+  const int rin = nsdb::CVR_TR + KH - 1;
+  if (!(o.force_generic == 0 && stride == 1 && dil == 1 && pad == 0 && KW <= 8 && W % 8 == 0 &&
+        C * KH <= 4 * nsdb::CVR_NKS && C * rin <= nsdb::CVR_ROWS && OW <= 16 * nsdb::CVR_MAXT))
+    return NSDB_CONV_IGEMM;
+  nsdb::ConvRowParams q{};
+  q.N = N; q.C = C; q.H = H; q.W = W; q.OC = OC; q.KH = KH; q.KW = KW; q.OH = OH; q.OW = OW; q.ldw = ldw;
+  q.rin = rin; q.ckh = C * KH; q.nks = (C * KH + 3) / 4;
+  q.ntiles = (OW + 15) / 16;
+  q.chunks = std::min((16 * q.ntiles + 4 + 7) / 8, nsdb::CVR_CP / 16);
+  q.groups_per_img = (OH + nsdb::CVR_TR - 1) / nsdb::CVR_TR;
+  q.ngroups = N * q.groups_per_img;
+  q.nchw_out = nchw_out; q.out_f32 = out_f32;
+  q.contig = o.contig;
+  q.segs = (4 * OW + 3) & ~3;
+  if ((q.segs / 2) % 4 == 0) q.segs += 4;
+  q.vec8 = ((long long)OH * OW) % 4 == 0 && out_align8;
+  if (32 * q.segs * 2 > nsdb::CVR_OSTAGE) return NSDB_CONV_IGEMM;
+  if ((long long)N * OC * OH * OW * 2 >= 0x7ffffff0LL) return NSDB_CONV_IGEMM;    // 31-bit buffer offsets
+  if (C * rin * q.chunks > 512 || 64 * ldw / 8 > 6 * 256 || 64 * ldw * 2 > nsdb::CVR_BUF) return NSDB_CONV_IGEMM;
+  if (q_out) *q_out = q;
+  const bool staged = nchw_out && !out_f32 && (OW & 1) == 0 && q.vec8 && ((OH % 4) * OW) % 4 == 0;
+  if (staged && o.variant == 0 && o.kernel && q.ntiles == nsdb::CVF_NT && 4 * OW <= nsdb::CVF_SEGS) {
+    if (o.kernel == 2 || o.kernel == 3 || o.kernel == 4) return NSDB_CONV_DIAG;
+    if (o.kernel == 6 && has_wfrag) return NSDB_CONV_DIAG;
+    if (o.kernel == 5 && has_wfrag) return NSDB_CONV_WS;
+    return NSDB_CONV_ROWFULL;
+  }
+  if (o.variant != 0) return NSDB_CONV_DIAG;
+  return staged ? NSDB_CONV_ROWS_STAGED : NSDB_CONV_ROWS;
+}
+
+static ConvOpts conv_default_opts() { return ConvOpts{0, 0, 512, 5, 0}; }
+
+// The plan of a call whose output is 8-B aligned (every tensor the bindings allocate is).
+int nsdb_conv2d_plan(int N, int C, int H, int W, int OC, int KH, int KW, int stride, int pad, int dil, int ldw,
+                     int nchw_out, int out_f32, int has_wfrag, const ConvOpts* opts) {
+  return conv_plan(N, C, H, W, OC, KH, KW, stride, pad, dil, ldw, nchw_out, out_f32, has_wfrag, 1,
+                   opts ? *opts : conv_default_opts(), nullptr);
+}
+
 int nsdb_conv2d_igemm(const void* X, const void* Wt, const float* bias, void* out, int N, int C, int H,
                       int W, int OC, int KH, int KW, int stride, int pad, int dil, int ldw, int act,
                       int nchw_out, int out_f32, const void* wfrag, const ConvOpts* opts, hipStream_t stream) {
-  const ConvOpts o = opts ? *opts : ConvOpts{0, 0, 512, 5, 0};
-  nsdb::ConvParams p;
-  p.X = (const unsigned short*)X; p.Wt = (const unsigned short*)Wt; p.bias = bias; p.out = out;
-  p.N = N; p.C = C; p.H = H; p.W = W; p.OC = OC; p.KH = KH; p.KW = KW;
-  p.stride = stride; p.pad = pad; p.dil = dil;
-  p.OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
-  p.OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
-  p.K = C * KH * KW; p.ldw = ldw;
-  if (ldw % 8 != 0 || ldw < p.K || p.OH <= 0 || p.OW <= 0) return -1;
-  if ((long long)N * C * H * W >= 0x7fffffffLL) return -2;   // 32-bit image offsets
-  p.act = act; p.nchw_out = nchw_out; p.out_f32 = out_f32;
-  // row-tiled LDS kernel for small-C, wide-row layers (see conv2d_rows_kernel)
-  const int rin = nsdb::CVR_TR + KH - 1;
-  if (o.force_generic == 0 && stride == 1 && dil == 1 && pad == 0 && KW <= 8 && W % 8 == 0 &&
-      C * KH <= 4 * nsdb::CVR_NKS && C * rin <= nsdb::CVR_ROWS && p.OW <= 16 * nsdb::CVR_MAXT) {
-    nsdb::ConvRowParams q;
-    q.X = p.X; q.Wt = p.Wt; q.bias = bias; q.out = out;
-    q.N = N; q.C = C; q.H = H; q.W = W; q.OC = OC; q.KH = KH; q.KW = KW; q.OH = p.OH; q.OW = p.OW; q.ldw = ldw;
-    q.rin = rin; q.ckh = C * KH; q.nks = (C * KH + 3) / 4;
-    q.ntiles = (p.OW + 15) / 16;
-    q.chunks = std::min((16 * q.ntiles + 4 + 7) / 8, nsdb::CVR_CP / 16);
-    q.groups_per_img = (p.OH + nsdb::CVR_TR - 1) / nsdb::CVR_TR;
-    q.ngroups = N * q.groups_per_img;
-    q.act = act; q.nchw_out = nchw_out; q.out_f32 = out_f32; q.variant = o.variant;
-    q.contig = o.contig;
-    q.Wfrag = (const unsigned short*)wfrag;
-    q.segs = (4 * p.OW + 3) & ~3;
-    if ((q.segs / 2) % 4 == 0) q.segs += 4;
-    q.vec8 = ((long long)p.OH * p.OW) % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0;
-    if (32 * q.segs * 2 > nsdb::CVR_OSTAGE) goto generic;
-    if ((long long)N * OC * p.OH * p.OW * 2 >= 0x7ffffff0LL) goto generic;    // 31-bit buffer offsets
-    if (C * rin * q.chunks > 512 || 64 * ldw / 8 > 6 * 256 || 64 * ldw * 2 > nsdb::CVR_BUF) goto generic;
-    {
-      const int blocks = o.max_blocks > 0 ? std::min(q.ngroups, o.max_blocks) : q.ngroups;
-      const dim3 grid(blocks, (OC + 63) / 64);
-      const bool staged = nchw_out && !out_f32 && (p.OW & 1) == 0 && q.vec8 && ((p.OH % 4) * p.OW) % 4 == 0;
-      if (staged && q.variant == 0 && o.kernel && q.ntiles == nsdb::CVF_NT && 4 * p.OW <= nsdb::CVF_SEGS) {
-        // one block of 4 waves per CU (one wave per SIMD), persistent over the row groups
-        const dim3 gridf(std::min(q.ngroups, o.max_blocks > 0 ? std::min(o.max_blocks, 256) : q.ngroups),
-                         (OC + 63) / 64);
-#define NSDB_CVF_LAUNCH(A) hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<A, false, true>), gridf, dim3(256), 0, stream, q)
-        if (o.kernel == 2 || o.kernel == 3) {   // phase-stamp timing builds (diagnostic)
-          if (o.kernel == 2)
-            hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, true, true>), gridf, dim3(256), 0, stream, q);
-          else
-            hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, true, false>), gridf, dim3(256), 0, stream, q);
-          return (int)hipGetLastError();
-        }
-        if (o.kernel == 4) {   // unpipelined stores (A/B)
-          hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, false, false>), gridf, dim3(256), 0, stream, q);
-          return (int)hipGetLastError();
-        }
-        if (o.kernel == 6 && wfrag != nullptr) {   // warp-specialised, phase-stamp timing build (diagnostic)
-          hipLaunchKernelGGL((nsdb::conv2d_ws_kernel<nsdb::ACT_NONE, true>), gridf, dim3(512), 0, stream, q);
-          return (int)hipGetLastError();
-        }
-        if (o.kernel == 5 && wfrag != nullptr) {   // warp-specialised: 4 compute + 4 store waves per CU
+  const ConvOpts o = opts ? *opts : conv_default_opts();
+  nsdb::ConvRowParams q;
+  const int plan = conv_plan(N, C, H, W, OC, KH, KW, stride, pad, dil, ldw, nchw_out, out_f32, wfrag != nullptr,
+                             (reinterpret_cast<uintptr_t>(out) & 7) == 0, o, &q);
+  if (plan < 0) return plan;
+  if (plan == NSDB_CONV_IGEMM) {
+    nsdb::ConvParams p;
+    p.X = (const unsigned short*)X; p.Wt = (const unsigned short*)Wt; p.bias = bias; p.out = out;
+    p.N = N; p.C = C; p.H = H; p.W = W; p.OC = OC; p.KH = KH; p.KW = KW;
+    p.stride = stride; p.pad = pad; p.dil = dil;
+    p.OH = (H + 2 * pad - dil * (KH - 1) - 1) / stride + 1;
+    p.OW = (W + 2 * pad - dil * (KW - 1) - 1) / stride + 1;
+    p.K = C * KH * KW; p.ldw = ldw;
+    p.act = act; p.nchw_out = nchw_out; p.out_f32 = out_f32;
+    const long long P = (long long)N * p.OH * p.OW;
+    dim3 grid((unsigned)((P + nsdb::CV_BM - 1) / nsdb::CV_BM), (OC + nsdb::CV_BN - 1) / nsdb::CV_BN);
+    hipLaunchKernelGGL(nsdb::conv2d_igemm_kernel, grid, dim3(256), 0, stream, p);
+    return (int)hipGetLastError();
+  }
+  q.X = (const unsigned short*)X; q.Wt = (const unsigned short*)Wt; q.bias = bias; q.out = out;
+  q.act = act; q.variant = o.variant;
+  q.Wfrag = (const unsigned short*)wfrag;
+  const dim3 grid(o.max_blocks > 0 ? std::min(q.ngroups, o.max_blocks) : q.ngroups, (OC + 63) / 64);
+  // full-row / warp-specialised: one block per CU, persistent over the row groups
+  const dim3 gridf(std::min(q.ngroups, o.max_blocks > 0 ? std::min(o.max_blocks, 256) : q.ngroups), (OC + 63) / 64);
+#define NSDB_CONV_ACT_SWITCH(LAUNCH)                         \
+  switch (act) {                                             \
+    case nsdb::ACT_RELU: LAUNCH(nsdb::ACT_RELU); break;       \
+    case nsdb::ACT_SIGMOID: LAUNCH(nsdb::ACT_SIGMOID); break; \
+    case nsdb::ACT_EXP: LAUNCH(nsdb::ACT_EXP); break;         \
+    case nsdb::ACT_TANH: LAUNCH(nsdb::ACT_TANH); break;       \
+    default: LAUNCH(nsdb::ACT_NONE); break;                   \
+  }
+  const bool staged = plan == NSDB_CONV_ROWS_STAGED;
+  if (plan == NSDB_CONV_DIAG && o.variant == 0) {   // timing builds of the 7-tile kernels, no activation
+    if (o.kernel == 2)        // full-row, phase stamps
+      hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, true, true>), gridf, dim3(256), 0, stream, q);
+    else if (o.kernel == 3)   // full-row, phase stamps, unpipelined stores
+      hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, true, false>), gridf, dim3(256), 0, stream, q);
+    else if (o.kernel == 4)   // full-row, unpipelined stores (A/B)
+      hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<nsdb::ACT_NONE, false, false>), gridf, dim3(256), 0, stream, q);
+    else                      // kernel 6: warp-specialised, phase stamps
+      hipLaunchKernelGGL((nsdb::conv2d_ws_kernel<nsdb::ACT_NONE, true>), gridf, dim3(512), 0, stream, q);
+  } else if (plan == NSDB_CONV_WS) {        // 4 compute + 4 store waves per CU
 #define NSDB_CVW_LAUNCH(A) hipLaunchKernelGGL((nsdb::conv2d_ws_kernel<A, false>), gridf, dim3(512), 0, stream, q)
-          switch (act) {
-            case nsdb::ACT_RELU: NSDB_CVW_LAUNCH(nsdb::ACT_RELU); break;
-            case nsdb::ACT_SIGMOID: NSDB_CVW_LAUNCH(nsdb::ACT_SIGMOID); break;
-            case nsdb::ACT_EXP: NSDB_CVW_LAUNCH(nsdb::ACT_EXP); break;
-            case nsdb::ACT_TANH: NSDB_CVW_LAUNCH(nsdb::ACT_TANH); break;
-            default: NSDB_CVW_LAUNCH(nsdb::ACT_NONE); break;
-          }
+    NSDB_CONV_ACT_SWITCH(NSDB_CVW_LAUNCH)
 #undef NSDB_CVW_LAUNCH
-          return (int)hipGetLastError();
-        }
-        switch (act) {
-          case nsdb::ACT_RELU: NSDB_CVF_LAUNCH(nsdb::ACT_RELU); break;
-          case nsdb::ACT_SIGMOID: NSDB_CVF_LAUNCH(nsdb::ACT_SIGMOID); break;
-          case nsdb::ACT_EXP: NSDB_CVF_LAUNCH(nsdb::ACT_EXP); break;
-          case nsdb::ACT_TANH: NSDB_CVF_LAUNCH(nsdb::ACT_TANH); break;
-          default: NSDB_CVF_LAUNCH(nsdb::ACT_NONE); break;
-        }
+  } else if (plan == NSDB_CONV_ROWFULL) {   // one wave per SIMD
+#define NSDB_CVF_LAUNCH(A) hipLaunchKernelGGL((nsdb::conv2d_rowfull_kernel<A, false, true>), gridf, dim3(256), 0, stream, q)
+    NSDB_CONV_ACT_SWITCH(NSDB_CVF_LAUNCH)
 #undef NSDB_CVF_LAUNCH
-        return (int)hipGetLastError();
-      }
-      if (q.variant != 0) {   // diagnostics build (timing only): runtime variant bits, no activation
-        if (staged) hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<nsdb::ACT_NONE, true, true>), grid, dim3(256), 0, stream, q);
-        else hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<nsdb::ACT_NONE, false, true>), grid, dim3(256), 0, stream, q);
-        return (int)hipGetLastError();
-      }
+  } else if (plan == NSDB_CONV_DIAG) {      // timing build of the two-pass kernel: runtime variant bits, no activation
+    const bool st = nchw_out && !out_f32 && (q.OW & 1) == 0 && q.vec8 && ((q.OH % 4) * q.OW) % 4 == 0;
+    if (st) hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<nsdb::ACT_NONE, true, true>), grid, dim3(256), 0, stream, q);
+    else hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<nsdb::ACT_NONE, false, true>), grid, dim3(256), 0, stream, q);
+  } else {                                  // NSDB_CONV_ROWS_STAGED / NSDB_CONV_ROWS
 #define NSDB_CVR_LAUNCH(A)                                                                                      \
   do {                                                                                                        \
     if (staged) hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<A, true, false>), grid, dim3(256), 0, stream, q); \
     else hipLaunchKernelGGL((nsdb::conv2d_rows_kernel<A, false, false>), grid, dim3(256), 0, stream, q);       \
   } while (0)
-      switch (act) {
-        case nsdb::ACT_RELU: NSDB_CVR_LAUNCH(nsdb::ACT_RELU); break;
-        case nsdb::ACT_SIGMOID: NSDB_CVR_LAUNCH(nsdb::ACT_SIGMOID); break;
-        case nsdb::ACT_EXP: NSDB_CVR_LAUNCH(nsdb::ACT_EXP); break;
-        case nsdb::ACT_TANH: NSDB_CVR_LAUNCH(nsdb::ACT_TANH); break;
-        default: NSDB_CVR_LAUNCH(nsdb::ACT_NONE); break;
-      }
+    NSDB_CONV_ACT_SWITCH(NSDB_CVR_LAUNCH)
 #undef NSDB_CVR_LAUNCH
-      return (int)hipGetLastError();
-    }
   }
-generic:
-  const long long P = (long long)N * p.OH * p.OW;
-  dim3 grid((unsigned)((P + nsdb::CV_BM - 1) / nsdb::CV_BM), (OC + nsdb::CV_BN - 1) / nsdb::CV_BN);
-  hipLaunchKernelGGL(nsdb::conv2d_igemm_kernel, grid, dim3(256), 0, stream, p);
+#undef NSDB_CONV_ACT_SWITCH
   return (int)hipGetLastError();
 }
 

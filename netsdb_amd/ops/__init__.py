@@ -349,17 +349,46 @@ def _kopt(name, default):
     return getattr(_KOPTS, "d", {}).get(name, default)
 
 
+CONV_MAX_IMAGE_BYTES = 0x7FFFFFF0      # conv2d.hip: a masked load's byte offset; the bf16 image set must end below it
+
+
+def _conv_packs_filter(C, KH, KW, stride, pad, dil) -> bool:
+    """Shapes for which ``conv2d`` hands the kernels the MFMA-fragment packed filter (conv_filter_fragments)."""
+    return stride == 1 and dil == 1 and pad == 0 and KW <= 8 and C * KH <= 24
+
+
+def conv2d_plan(N, C, H, W, OC, KH, KW, stride=1, pad=0, dil=1, ldw=None, nchw_out=False,
+                out_dtype=torch.bfloat16, has_wfrag=None) -> str:
+    """The kernel a GPU ``conv2d`` call of this geometry gets under the calling thread's ``kernel_options``: "igemm"
+    (generic gather), "rows" / "rows_staged" (two-pass row kernel, direct / LDS-staged stores), "rowfull", "ws"
+    (warp-specialised) or "diag" (a timing build: conv_kernel 2/3/4/6 or conv_variant != 0, whose output is not the
+    convolution). Host arithmetic only: the same function of conv2d.hip that the launch itself consults. ``ldw`` is
+    the filter's row length (default K rounded up to 8); ``has_wfrag`` defaults to what ``conv2d`` would pass."""
+    if ldw is None:
+        ldw = (C * KH * KW + 7) // 8 * 8
+    if has_wfrag is None:
+        has_wfrag = _conv_packs_filter(C, KH, KW, stride, pad, dil)
+    return _ext.hip().conv2d_plan(N, C, H, W, OC, KH, KW, stride, pad, dil, ldw, bool(nchw_out),
+                                  out_dtype == torch.float32, bool(has_wfrag), int(_kopt("conv_kernel", -1)),
+                                  int(_kopt("conv_blocks", -1)), bool(_kopt("conv_generic", False)),
+                                  int(_kopt("conv_variant", 0)), int(_kopt("conv_contig", 0)))
+
+
 def conv2d(X, Wflat, bias=None, KH=1, KW=1, stride=1, pad=0, dil=1, act=ACT_NONE, nchw_out=False,
            out_dtype=torch.bfloat16):
-    """Fused implicit-GEMM conv. X [N,C,H,W]; Wflat [OC, >=C*KH*KW] in (c,kh,kw) im2col order. Launch options
-    come from the calling thread's ``kernel_options`` scope."""
+    """Fused implicit-GEMM conv. X [N,C,H,W]; Wflat [OC, >=C*KH*KW] in (c,kh,kw) im2col order, zero in the columns
+    past C*KH*KW. Launch options come from the calling thread's ``kernel_options`` scope; ``conv2d_plan`` names the
+    kernel a call gets. The bf16 image set must be smaller than 0x7ffffff0 bytes (RuntimeError otherwise). The row
+    kernels ("rows", "rows_staged", "rowfull", "ws") read 8 taps per filter row with zero weights past KW, so a NaN or
+    Inf pixel at column c makes outputs ow in [c-7, c] of its rows non-finite, not only [c-KW+1, c] as in the generic
+    kernel and the CPU path."""
     act = act_code(act)
     if _use_hip(X, Wflat):
         if bias is not None and bias.dtype != torch.float32:
             bias = bias.float()
         C = X.shape[1]
         wfrag = None
-        if stride == 1 and dil == 1 and pad == 0 and KW <= 8 and C * KH <= 24:
+        if _conv_packs_filter(C, KH, KW, stride, pad, dil):
             # small-C row-kernel shapes: the packed B fragments (cached per filter tensor and version)
             wfrag = derived(Wflat, f"conv_frag_{C}_{KH}_{KW}", lambda t: conv_filter_fragments(t, C, KH, KW))
         return _ext.hip().conv2d(X, Wflat, bias, KH, KW, stride, pad, dil, act, bool(nchw_out),
@@ -368,6 +397,8 @@ def conv2d(X, Wflat, bias=None, KH=1, KW=1, stride=1, pad=0, dil=1, act=ACT_NONE
                                  int(_kopt("conv_variant", 0)), int(_kopt("conv_contig", 0)))
     N, C = X.shape[0], X.shape[1]
     OC = Wflat.shape[0]
+    if X.numel() * 2 >= CONV_MAX_IMAGE_BYTES:
+        raise RuntimeError("conv2d: image set too large (the kernels address it with 31-bit byte offsets)")
     w = Wflat[:, : C * KH * KW].float().reshape(OC, C, KH, KW)
     y = torch.nn.functional.conv2d(X.float(), w, bias.float() if bias is not None else None, stride, pad, dil)
     y = _apply_act(y, act)
@@ -382,9 +413,13 @@ def im2col(X, KH, KW, stride=1, pad=0, dil=1, ldk=None):
     ldk = ldk or (K + 7) // 8 * 8
     if _use_hip(X):
         return _ext.hip().im2col(X, KH, KW, stride, pad, dil, ldk)
-    cols = torch.nn.functional.unfold(X.float(), (KH, KW), dilation=dil, padding=pad, stride=stride)
-    cols = cols.transpose(1, 2).reshape(-1, K)
-    return torch.nn.functional.pad(cols, (0, ldk - K)).to(X.dtype)
+    # a pure gather, like the kernel: 16-bit elements travel as their bit patterns (exact in f64), so NaN payloads,
+    # -0 and denormals come out as they went in
+    bits = {2: torch.int16, 4: torch.int32}.get(X.element_size()) if X.is_floating_point() else None
+    src = X.view(bits).double() if bits is not None else X.double()
+    cols = torch.nn.functional.unfold(src, (KH, KW), dilation=dil, padding=pad, stride=stride)
+    cols = torch.nn.functional.pad(cols.transpose(1, 2).reshape(-1, K), (0, ldk - K))
+    return cols.to(bits).view(X.dtype) if bits is not None else cols.to(X.dtype)
 
 
 _PREFETCH_SINK = {}
