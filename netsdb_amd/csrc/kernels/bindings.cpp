@@ -11,10 +11,11 @@
 #include <mutex>
 #include <utility>
 
+#include "gemm_plan.h"
+
 extern "C" {
 int nsdb_gemm_splits(int M, int N, int K, int batch, int cfg);
 int nsdb_gemm_prefetch_eligible(int M, int N, int K, int batch, int splits, int cfg);
-int nsdb_gemm_launch_wgs(int M, int N, int K, int batch, int splits, int cfg);
 int nsdb_gemm_nt_bf16(const void* A, const void* B, void* C, float* ws, const float* bias, int M, int N, int K,
                       long long lda, long long ldb, long long ldc, long long sA, long long sB, long long sC,
                       long long sBias, int batch, int splits, int act, int bias_mode, int out_f32, float alpha,
@@ -119,9 +120,17 @@ bool is_f32(const torch::Tensor& t, const char* name) {
   return t.scalar_type() == torch::kFloat32;
 }
 
+// cfg 5 / 6 name the stream tiles 3 / 4 with k-interleaved splits (split s takes k-tiles s, s + S, ...; an A/B arm):
+// maps cfg to the tile config and returns the kinter request.
+int take_kinter(int64_t& cfg) {
+  const int kinter = cfg >= 5 ? 1 : 0;
+  if (kinter) cfg -= 2;
+  return kinter;
+}
+
 // C = epi(alpha * A @ B^T); A [b?,M,K] bf16, B [b?,N,K] bf16 (row stride may exceed K), bias f32.
 // cfg: -1 auto, 0 (128x128 tile kernel), 2 (256x256 8-phase), 3 / 4 (256x128 / 128x256 skinny stream). prefetch: a later kernel's operand that this
-// launch's workgroups read into the Infinity Cache as they finish (the caller checked gemm_prefetch_eligible).
+// launch's workgroups read into the Infinity Cache as they finish (the caller checked the plan's prefetch_eligible).
 torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Tensor> bias, int64_t bias_mode,
                       int64_t act, bool out_f32, double alpha, double dropout, int64_t seed, int64_t splits,
                       c10::optional<torch::Tensor> out, bool accumulate, int64_t cfg, int64_t epi,
@@ -165,30 +174,38 @@ torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Ten
     TORCH_CHECK(C.size(-2) == M && C.size(-1) == N && C.stride(-1) == 1, "out shape mismatch");
   } else {
     TORCH_CHECK(!accumulate, "accumulate=True needs an existing f32 out tensor");
-    C = batched ? torch::empty({batch, M, N}, opts) : torch::empty({M, N}, opts);
   }
   TORCH_CHECK(!accumulate || out_f32, "accumulate=True needs out_f32");
   TORCH_CHECK(cfg == -1 || cfg == 0 || (cfg >= 2 && cfg <= 6),
               "gemm_nt: cfg must be -1 (auto), 0, 2, 3, 4, 5 or 6 (study configs: _hip_study)");
-  // 5 / 6: the stream tiles 3 / 4 with k-interleaved splits (split s takes k-tiles s, s + S, ...; an A/B arm)
-  const int kinter = cfg >= 5 ? 1 : 0;
-  if (cfg >= 5) cfg -= 2;
-  int s = splits > 0 ? (int)splits : nsdb_gemm_splits((int)M, (int)N, (int)K, (int)batch, (int)cfg);
-  torch::Tensor ws;
-  float* wsp = nullptr;
-  if (s > 1) {
-    ws = torch::empty({batch * s * M * N}, A.options().dtype(torch::kFloat32));
-    wsp = ws.data_ptr<float>();
-  }
+  const int kinter = take_kinter(cfg);
   TORCH_CHECK(epi >= -1 && epi <= 1, "gemm_nt: epi must be -1 (auto), 0 (LDS-staged) or 1 (direct)");
   TORCH_CHECK(mfma == 0 || mfma == 16 || mfma == 32, "gemm_nt: mfma must be 0 (auto), 16 or 32");
+  // the launcher's own plan for this call, before anything is allocated: C (contiguous and 16-B aligned when it is
+  // allocated here), the split-K workspace and the fix-up state are sized from it
+  nsdb::GemmCall call;
+  call.M = (int)M; call.N = (int)N; call.K = (int)K; call.batch = (int)batch; call.splits = (int)splits;
+  call.cfg = (int)cfg; call.epi = (int)epi; call.mfma = (int)mfma; call.fixup = fixup ? 1 : 0; call.kinter = kinter;
+  call.out_f32 = out_f32 ? 1 : 0; call.accumulate = accumulate ? 1 : 0; call.bias_mode = bptr ? (int)bias_mode : 0;
+  call.lda = A.stride(-2); call.ldb = B.stride(-2);
+  call.ldc = C.defined() ? C.stride(-2) : N;
+  call.sC = !batched ? 0 : C.defined() ? C.stride(0) : M * N;
+  call.c_align = C.defined() ? nsdb::gemm_ptr_align(C.data_ptr()) : 16;
+  const nsdb::GemmPlan plan = nsdb::gemm_plan(call);
+  check_rc(plan.rc, "gemm_nt");
+  if (!C.defined()) C = batched ? torch::empty({batch, M, N}, opts) : torch::empty({M, N}, opts);
+  torch::Tensor ws;
+  float* wsp = nullptr;
+  if (plan.splits > 1) {
+    ws = torch::empty({batch * plan.splits * M * N}, A.options().dtype(torch::kFloat32));
+    wsp = ws.data_ptr<float>();
+  }
   GemmOpts o{(int)cfg, (int)epi, nullptr, 0, kinter, (int)mfma, 0, nullptr};
-  if (fixup && s > 1) {
+  if (plan.kernel == nsdb::GEMM_8PH_FIXUP) {
     // the in-launch split-K reduction's arrival / departure words: zero between launches on this stream (shared
     // with the fused softmax's, which also leaves them zero)
-    const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
     o.fixup = 1;
-    o.fx_state = softmax_state(A, 2 * tiles, cur_stream()).data_ptr<int>();
+    o.fx_state = softmax_state(A, 2 * (int64_t)plan.tiles_m * plan.tiles_n, cur_stream()).data_ptr<int>();
   }
   if (prefetch.has_value() && prefetch->defined() && prefetch->numel() > 0) {
     // the byte span of the tensor's elements (a strided view reads its whole span)
@@ -201,7 +218,7 @@ torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Ten
   const int rc = nsdb_gemm_nt_bf16(
       A.data_ptr(), B.data_ptr(), C.data_ptr(), wsp, bptr, (int)M, (int)N, (int)K, A.stride(-2), B.stride(-2),
       C.stride(-2), batched ? A.stride(0) : 0, batched ? B.stride(0) : 0, batched ? C.stride(0) : 0, sBias,
-      (int)batch, s, (int)act, (int)bias_mode, out_f32 ? 1 : 0, (float)alpha, (float)dropout,
+      (int)batch, (int)splits, (int)act, (int)bias_mode, out_f32 ? 1 : 0, (float)alpha, (float)dropout,
       (unsigned long long)seed, accumulate ? 1 : 0, 0, 0, &o, cur_stream());
   check_rc(rc, "gemm_nt");
   return C;
@@ -294,6 +311,7 @@ torch::Tensor gemm_nt_bseg(torch::Tensor A, torch::Tensor Bg, c10::optional<torc
   TORCH_CHECK(A.size(1) == K, "A K must equal S*seg_k");
   const float* bptr = nullptr;
   if (bias.has_value() && bias->defined()) {
+    check_same_device(*bias, A, "bias");
     TORCH_CHECK(bias->scalar_type() == torch::kFloat32 && bias->is_contiguous() && bias->dim() == 1, "bias f32 1-D");
     TORCH_CHECK(bias->numel() == (bias_mode == 1 ? M : N), "bias length mismatch");
     bptr = bias->data_ptr<float>();
@@ -306,17 +324,26 @@ torch::Tensor gemm_nt_bseg(torch::Tensor A, torch::Tensor Bg, c10::optional<torc
   } else {
     C = torch::empty({M, N}, opts);
   }
-  // splits: S segments x d splits per segment (d | seg_k/64), close to the launcher's own choice
-  const int auto_s = std::max<int>(1, nsdb_gemm_splits((int)M, (int)N, (int)K, 1, -1));
+  // splits: S segments x d splits per segment (d | seg_k/64), close to the launcher's own choice; the plan of that
+  // request gives the effective count, which sizes the workspace
+  nsdb::GemmCall call;
+  call.M = (int)M; call.N = (int)N; call.K = (int)K;
+  call.out_f32 = out_f32 ? 1 : 0; call.bias_mode = bptr ? (int)bias_mode : 0;
+  call.lda = A.stride(0); call.ldb = segk; call.ldc = C.stride(0); call.c_align = nsdb::gemm_ptr_align(C.data_ptr());
+  const int auto_s = nsdb::gemm_plan(call).splits;
   const int steps = (int)(segk / 64);
   int d = 1;
   for (int c = 1; c <= steps; ++c)
     if (steps % c == 0 && S * c <= std::max<int64_t>(auto_s, S)) d = c;
   const int s = (int)(S * d);
+  call.splits = s;
+  call.seg_k = segk;
+  const nsdb::GemmPlan plan = nsdb::gemm_plan(call);
+  check_rc(plan.rc, "gemm_nt_bseg");
   torch::Tensor ws;
   float* wsp = nullptr;
-  if (s > 1) {
-    ws = torch::empty({(int64_t)s * M * N}, A.options().dtype(torch::kFloat32));
+  if (plan.splits > 1) {
+    ws = torch::empty({(int64_t)plan.splits * M * N}, A.options().dtype(torch::kFloat32));
     wsp = ws.data_ptr<float>();
   }
   const int rc = nsdb_gemm_nt_bf16(A.data_ptr(), Bg.data_ptr(), C.data_ptr(), wsp, bptr, (int)M, (int)N, (int)K,
@@ -355,6 +382,35 @@ torch::Tensor gemm_nt_f32(torch::Tensor A, torch::Tensor B, double alpha, c10::o
 
 int64_t gemm_splits(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t cfg) {
   return nsdb_gemm_splits((int)M, (int)N, (int)K, (int)batch, (int)cfg);
+}
+
+// The plan nsdb_gemm_nt_bf16 follows for a gemm_nt call of this shape and these options with K-contiguous operands and
+// C rows of ldc elements (-1: N) at a c_align-byte aligned address (host arithmetic only, no tensors).
+py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t splits, int64_t cfg, int64_t epi, int64_t mfma,
+                   int64_t fixup, bool out_f32, bool accumulate, int64_t bias_mode, int64_t ldc, int64_t c_align,
+                   int64_t seg_k) {
+  nsdb::GemmCall call;
+  call.kinter = take_kinter(cfg);
+  call.M = (int)M; call.N = (int)N; call.K = (int)K; call.batch = (int)batch; call.splits = (int)splits;
+  call.cfg = (int)cfg; call.epi = (int)epi; call.mfma = (int)mfma; call.fixup = fixup ? 1 : 0;
+  call.out_f32 = out_f32 ? 1 : 0; call.accumulate = accumulate ? 1 : 0; call.bias_mode = (int)bias_mode;
+  call.lda = K;
+  call.ldb = seg_k > 0 ? seg_k : K;
+  call.ldc = ldc < 0 ? N : ldc;
+  call.sC = batch > 1 ? M * call.ldc : 0;
+  call.c_align = (int)c_align; call.seg_k = seg_k;
+  const nsdb::GemmPlan p = nsdb::gemm_plan(call);
+  check_rc(p.rc, "gemm_plan");
+  py::dict d;
+  d["kernel"] = nsdb::gemm_kernel_name(p.kernel);
+  d["cfg"] = p.cfg;
+  d["splits"] = p.splits;
+  d["reducer"] = nsdb::gemm_reducer_name(p.reducer);
+  d["direct_epi"] = p.direct_epi != 0;
+  d["kinter"] = p.kinter != 0;
+  d["wgs"] = p.wgs;
+  d["prefetch_eligible"] = p.prefetch_eligible != 0;
+  return d;
 }
 
 torch::Tensor conv2d(torch::Tensor X, torch::Tensor Wt, c10::optional<torch::Tensor> bias, int64_t KH, int64_t KW,
@@ -787,10 +843,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dropout") = 0.0, py::arg("seed") = 0, py::arg("splits") = 0, py::arg("out") = py::none(),
         py::arg("accumulate") = false, py::arg("cfg") = -1, py::arg("epi") = -1, py::arg("prefetch") = py::none(),
         py::arg("mfma") = 0, py::arg("fixup") = 0);
-  m.def("gemm_launch_wgs", [](int64_t M, int64_t N, int64_t K, int64_t batch, int64_t splits, int64_t cfg) {
-          return (int64_t)nsdb_gemm_launch_wgs((int)M, (int)N, (int)K, (int)batch, (int)splits, (int)cfg);
-        }, "workgroups of the GEMM launch for this shape (splits <= 0: the launcher's choice)",
-        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("batch") = 1, py::arg("splits") = 0, py::arg("cfg") = -1);
+  m.def("gemm_plan", &gemm_plan, "the launch plan of a gemm_nt call (host arithmetic only)", py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("batch") = 1, py::arg("splits") = 0, py::arg("cfg") = -1, py::arg("epi") = -1,
+        py::arg("mfma") = 0, py::arg("fixup") = 0, py::arg("out_f32") = false, py::arg("accumulate") = false,
+        py::arg("bias_mode") = 0, py::arg("ldc") = -1, py::arg("c_align") = 16, py::arg("seg_k") = 0);
   m.def("prefetch", &prefetch, "warm the caches with a read of each tensor", py::arg("tensors"), py::arg("sink"),
         py::arg("blocks") = 64);
   m.def("gemm_nt_f32", &gemm_nt_f32, "alpha * A.B^T (+C) on the exact-f32 MFMA (16x16x4)", py::arg("A"),

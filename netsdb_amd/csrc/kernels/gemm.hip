@@ -1340,84 +1340,32 @@ struct GemmOpts {
   int* fx_state;            // its arrival / departure words ([2 * tiles] ints, zero between launches on a stream)
 };
 
+// GemmParams of a plain launch: unsplit, alpha 1, no bias / activation / dropout, no softmax, no diagnostics, every
+// pointer null. The launchers set the operands and what they use.
+static nsdb::GemmParams neutral_params() {
+  nsdb::GemmParams p{};
+  p.splits = 1;
+  p.alpha = 1.f;
+  p.steal_ch = 2;
+  return p;
+}
+
+// The plan of a launch described by its shape alone (contiguous operands, default options).
+static nsdb::GemmPlan shape_plan(int M, int N, int K, int batch, int splits, int cfg) {
+  nsdb::GemmCall c;
+  c.M = M; c.N = N; c.K = K; c.batch = batch; c.splits = splits; c.cfg = cfg;
+  c.lda = c.ldb = K; c.ldc = N;
+  return nsdb::gemm_plan(c);
+}
+
 extern "C" {
 
-// Tile config: the 256x256 8-phase tile (1 block/CU) when both dims fill it and there is enough work.
-static int pick_cfg(int M, int N, int K, int batch) {
-  const long long big_tiles = (long long)((M + 255) / 256) * ((N + 255) / 256) * batch;
-  const bool fills = M >= 192 && N >= 192;
-  const long long ksteps = (K + nsdb::BK - 1) / nsdb::BK;
-  // 8-phase 256^2 when there is a long mainloop, or when >= 3/4 of the CUs get a tile and K spans at
-  // least 16 k-tiles (the FF output layer 1000x14588x1000: 60 us vs 75 us for 128^2, kernel trace)
-  if (fills && (big_tiles * ksteps >= 256LL * 32 || (big_tiles >= 192 && ksteps >= 16))) return 2;
-  // skinny, very long K (the dedup scoring GEMMs 500 x 100 x 900k and 12 x 500 x 100 x 100k): memory-bound; the
-  // 8-phase kernel keeps three half-tiles of A in flight and zero-fills the missing B rows without reading them
-  // (common panel 205 vs 222 us, batched private panels 263 vs 285 us, profiles/r4_dedup)
-  // skinny (one side <= 128 rows) with a long K: the 256x128 / 128x256 stream tile (MFMA work padded to 128, not
-  // 256 rows; 2 k-tiles in flight per CU): 500x100x900k 208.7 vs 213.9 us, 12x500x100x100k 290.5 vs 292.9,
-  // 4096x128x16k 38.4 vs 40.7 (8-phase) / 43.8 (128^2) (profiles/r5_stream)
-  if (std::max(M, N) >= 192 && std::min(M, N) <= 128 && ksteps >= 256) return M >= N ? 3 : 4;
-  if ((M >= 192 || N >= 192) && std::min(M, N) >= 64 && ksteps >= 1024) return 2;
-  return 0;
-}
+// Number of split-K slices the launcher will use for config `cfg` (-1 auto).
+int nsdb_gemm_splits(int M, int N, int K, int batch, int cfg) { return shape_plan(M, N, K, batch, 0, cfg).splits; }
 
-// Macro tile of a config: 0 = 128x128, 2 = 256x256 8-phase, 3 = 256x128 stream, 4 = 128x256 stream.
-static void cfg_tile(int cfg, int& tbm, int& tbn) {
-  tbm = cfg == 2 || cfg == 3 ? 256 : nsdb::BM;
-  tbn = cfg == 2 || cfg == 4 ? 256 : nsdb::BN;
-}
-
-static int resolve_cfg(int cfg, int M, int N, int K, int batch) { return cfg < 0 ? pick_cfg(M, N, K, batch) : cfg; }
-
-// Number of split-K slices the launcher will use for config `cfg` (-1 auto); the caller sizes the workspace.
-int nsdb_gemm_splits(int M, int N, int K, int batch, int cfg) {
-  cfg = resolve_cfg(cfg, M, N, K, batch);
-  int tbm, tbn;
-  cfg_tile(cfg, tbm, tbn);
-  const int tiles = ((M + tbm - 1) / tbm) * ((N + tbn - 1) / tbn) * batch;
-  const int ksteps = (K + nsdb::BK - 1) / nsdb::BK;
-  // fill the chip: 256 CUs x (2 blocks of 128^2 | 1 block of 256^2); keep >= 8 k-steps per split
-  const int target = cfg ? 256 : 512;   // the 256^2 and stream tiles run one block per CU
-  int splits = 1;
-  // >= 3/4 of the chip busy: a split's f32 slabs + reduce pass cost more than the idle CUs (1000x14588x1024:
-  // 51 us + 24 us reduce with 2 splits vs 60 us unsplit)
-  if (tiles < target && !(cfg == 2 && tiles >= 192)) {
-    // round DOWN: tiles * splits stays within one wave of resident workgroups. Rounding up left a
-    // handful of workgroups for a second, nearly empty wave (6000x100x100k: 47 tiles x 11 splits =
-    // 517 WGs ran 456 us; x 10 = 470 WGs fit one wave)
-    splits = std::max(1, target / tiles);
-    splits = std::min(splits, std::max(1, ksteps / 8));
-  }
-  if (splits > 1) {
-    const int kchunk_steps = (ksteps + splits - 1) / splits;
-    splits = (ksteps + kchunk_steps - 1) / kchunk_steps;
-  }
-  return splits;
-}
-
-// Workgroups of the launch nsdb_gemm_nt_bf16 makes for this shape (splits <= 0: the launcher's own choice).
-int nsdb_gemm_launch_wgs(int M, int N, int K, int batch, int splits, int cfg) {
-  cfg = resolve_cfg(cfg, M, N, K, batch);
-  int tbm, tbn;
-  cfg_tile(cfg, tbm, tbn);
-  const int ksteps = (K + nsdb::BK - 1) / nsdb::BK;
-  if (splits <= 0) splits = nsdb_gemm_splits(M, N, K, batch, cfg);
-  splits = std::max(1, splits);
-  const int kchunk_steps = std::max(1, (ksteps + splits - 1) / splits);
-  const int s = std::max(1, (ksteps + kchunk_steps - 1) / kchunk_steps);
-  return ((M + tbm - 1) / tbm) * ((N + tbn - 1) / tbn) * s * batch;
-}
-
-// Would a launch of this shape take an operand prefetch (an 8-phase launch of >= 128 workgroups with >= 64
-// k-tiles per workgroup: a long, one-wave-resident GEMM whose finishing workgroups can warm the next operand)?
+// Would a launch of this shape take an operand prefetch (splits <= 0: the launcher's own choice)?
 int nsdb_gemm_prefetch_eligible(int M, int N, int K, int batch, int splits, int cfg) {
-  if (resolve_cfg(cfg, M, N, K, batch) != 2) return 0;
-  const int ksteps = (K + nsdb::BK - 1) / nsdb::BK;
-  if (splits <= 0) splits = nsdb_gemm_splits(M, N, K, batch, cfg);    // the launcher's own choice
-  splits = std::max(1, splits);
-  const int kchunk_steps = (ksteps + splits - 1) / splits;
-  const long long wgs = (long long)((M + 255) / 256) * ((N + 255) / 256) * ((ksteps + kchunk_steps - 1) / kchunk_steps) * batch;
-  return wgs >= 128 && kchunk_steps >= 64 ? 1 : 0;
+  return shape_plan(M, N, K, batch, splits, cfg).prefetch_eligible;
 }
 
 // C (f32) = softmax(alpha * A . B^T + bias) along axis 1 (each row of C) or 2 (each column of C), fused into
@@ -1429,126 +1377,108 @@ int nsdb_gemm_nt_softmax(const void* A, const void* B, float* C, const float* bi
                          int* flag, int* dep, int force_fallback, int epi, unsigned long long* stamps,
                          hipStream_t stream) {
   if (M <= 0 || N <= 0) return 0;
-  if (K % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0 || (axis != 1 && axis != 2)) return -1;
-  if (256LL * lda * 2 >= 0x7ffffff0LL || 256LL * ldb * 2 >= 0x7ffffff0LL) return -2;
-  nsdb::GemmParams p;
-  p.A = (const unsigned short*)A; p.B = (const unsigned short*)B; p.C = C; p.ws = nullptr; p.bias = bias;
-  p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.sA = p.sB = p.sC = p.sBias = 0;
+  if (axis != 1 && axis != 2) return -1;
+  // an unsplit f32 8-phase launch: the plan checks the operands (-1, -2) and gives the tiles, the one K chunk and
+  // whether the final values go straight from the registers (store_direct_8ph)
+  nsdb::GemmCall call;
+  call.M = M; call.N = N; call.K = K; call.splits = 1; call.cfg = 2; call.epi = epi; call.out_f32 = 1;
+  call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.c_align = nsdb::gemm_ptr_align(C);
+  const nsdb::GemmPlan plan = nsdb::gemm_plan(call);
+  if (plan.rc < 0) return plan.rc;
+  nsdb::GemmParams p = neutral_params();
+  p.A = (const unsigned short*)A; p.B = (const unsigned short*)B; p.C = C; p.bias = bias;
+  p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.M = M; p.N = N; p.K = K;
-  p.kchunk = std::max(1, (K + nsdb::BK - 1) / nsdb::BK) * nsdb::BK;
-  p.splits = 1;
-  p.act = 0; p.bias_mode = bias ? bias_mode : 0; p.out_f32 = 1; p.accumulate = 0;
-  p.alpha = alpha; p.dropout = 0.f; p.seed = 0; p.diag = force_fallback ? 4 : 0;
-  p.seg_k = 0; p.seg_stride_b = 0;
-  p.tiles_m = (M + 255) / 256;
-  p.tiles_n = (N + 255) / 256;
-  p.vec_ws = 0;
-  p.vec_c = (ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0) ? 1 : 0;
+  p.kchunk = plan.kchunk;
+  p.bias_mode = bias ? bias_mode : 0; p.out_f32 = 1;
+  p.alpha = alpha; p.diag = force_fallback ? 4 : 0;
+  p.tiles_m = plan.tiles_m;
+  p.tiles_n = plan.tiles_n;
+  p.vec_c = plan.vec_c;
   p.softmax = axis; p.sm_part = (float2*)part; p.sm_cnt = cnt; p.sm_flag = flag; p.sm_dep = dep; p.stamps = stamps;
-  p.adapt = nullptr;
-  p.signal = nullptr; p.signal_value = 0; p.steal_cnt = nullptr; p.steal_tq = 0; p.steal_ch = 2;
-  p.direct_epi = p.vec_c && epi != 0 ? 1 : 0;      // final values straight from registers (store_direct_8ph)
+  p.direct_epi = plan.direct_epi;
   const int tiles = p.tiles_m * p.tiles_n;
   if (axis == 1) hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<1>, dim3(tiles), dim3(512), 0, stream, p);
   else hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<2>, dim3(tiles), dim3(512), 0, stream, p);
   return (int)hipGetLastError();
 }
 
+// C = epilogue(alpha * A . B^T) as gemm_plan (gemm_plan.h) plans it: the same GemmCall gives the caller the same plan,
+// so it knows the workspace (ws: f32 [batch][plan.splits][M][N] when plan.splits > 1) and the fix-up state
+// (opts->fx_state: 2 * tiles ints when plan.kernel is the in-launch reduction) this launch needs. splits <= 0: the
+// plan's own choice. Returns the plan's rc (< 0: nothing launched) or the HIP launch error.
 int nsdb_gemm_nt_bf16(const void* A, const void* B, void* C, float* ws, const float* bias,
                       int M, int N, int K, long long lda, long long ldb, long long ldc,
                       long long sA, long long sB, long long sC, long long sBias, int batch,
                       int splits, int act, int bias_mode, int out_f32, float alpha, float dropout,
                       unsigned long long seed, int accumulate, long long seg_k, long long seg_stride_b,
                       const GemmOpts* opts, hipStream_t stream) {
-  if (M <= 0 || N <= 0 || batch <= 0) return 0;
-  if (K % 8 != 0 || lda % 8 != 0 || ldb % 8 != 0) return -1;        // 16-B rows for the LDS-DMA
-  if (256LL * lda * 2 >= 0x7ffffff0LL || 256LL * ldb * 2 >= 0x7ffffff0LL)
-    return -2;                                                         // per-tile buffer range
-  if (splits > 1 && ws == nullptr) return -3;
-  if (accumulate && !out_f32) return -4;                                // C += A.B^T only into f32
-  const int cfg = resolve_cfg(opts ? opts->cfg : -1, M, N, K, batch);
-  if (cfg < 0 || cfg > 4 || cfg == 1) return -8;                      // not a production config
-  nsdb::GemmParams p;
+  // 1. the call -> its plan (gemm_plan.h: every tile, split, epilogue and kernel decision)
+  nsdb::GemmCall call;
+  call.M = M; call.N = N; call.K = K; call.batch = batch; call.splits = splits;
+  if (opts) {
+    call.cfg = opts->cfg; call.epi = opts->epi; call.mfma = opts->mfma; call.kinter = opts->kinter;
+    call.fixup = opts->fixup && opts->fx_state;
+  }
+  call.out_f32 = out_f32; call.accumulate = accumulate; call.bias_mode = bias ? bias_mode : 0;
+  call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.sC = sC; call.c_align = nsdb::gemm_ptr_align(C);
+  call.seg_k = seg_k; call.has_ws = ws != nullptr;
+  const nsdb::GemmPlan plan = nsdb::gemm_plan(call);
+  if (plan.rc < 0 || plan.wgs == 0) return plan.rc;
+  // 2. the kernel parameters from the plan and the pointers
+  nsdb::GemmParams p = neutral_params();
   p.A = (const unsigned short*)A; p.B = (const unsigned short*)B; p.C = C; p.ws = ws; p.bias = bias;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.sA = sA; p.sB = sB; p.sC = sC; p.sBias = sBias;
   p.M = M; p.N = N; p.K = K;
-  const int ksteps = (K + nsdb::BK - 1) / nsdb::BK;
-  splits = std::max(1, splits);
-  const int kchunk_steps = (ksteps + splits - 1) / splits;
-  p.kchunk = std::max(1, kchunk_steps) * nsdb::BK;
-  p.splits = (K + p.kchunk - 1) / p.kchunk;
-  if (p.splits < 1) p.splits = 1;
-  p.act = act; p.bias_mode = bias ? bias_mode : 0; p.out_f32 = out_f32; p.accumulate = accumulate;
+  p.splits = plan.splits; p.kchunk = plan.kchunk;
+  p.act = act; p.bias_mode = call.bias_mode; p.out_f32 = out_f32; p.accumulate = accumulate;
   p.alpha = alpha; p.dropout = dropout; p.seed = seed;
-  p.diag = 0;
-  p.seg_k = seg_k;
-  p.seg_stride_b = seg_stride_b;
-  p.softmax = 0; p.sm_part = nullptr; p.sm_cnt = nullptr; p.sm_flag = nullptr;
-  p.stamps = nullptr; p.adapt = nullptr;
-  p.signal = nullptr; p.signal_value = 0; p.steal_cnt = nullptr; p.steal_tq = 0; p.steal_ch = 2;
-  if (seg_k > 0 && (seg_k % p.kchunk != 0 || seg_k % nsdb::BK != 0)) return -5;   // a split must not cross a segment
-  int tbm, tbn;
-  cfg_tile(cfg, tbm, tbn);
-  p.tiles_m = (M + tbm - 1) / tbm;
-  p.tiles_n = (N + tbn - 1) / tbn;
-  p.vec_ws = (N % 4 == 0) ? 1 : 0;
-  p.vec_c = (ldc % 4 == 0 && sC % 4 == 0 &&
-             (reinterpret_cast<uintptr_t>(C) & (out_f32 ? 15 : 7)) == 0) ? 1 : 0;
-  // the direct register epilogue for unsplit 8-phase launches with aligned C rows and for split-K slabs (opts->epi:
-  // -1 auto = direct, 0 = LDS-staged, 1 = direct); C += A.B^T and per-element bias keep the LDS-staged epilogue
-  const int epi_pref = opts ? opts->epi : -1;
-  // split-K slabs (N % 4 == 0) take the direct stores too
-  p.direct_epi = (cfg == 2 && epi_pref != 0 &&
-                  ((p.splits == 1 && !accumulate && p.vec_c && p.bias_mode != 3) || (p.splits > 1 && p.vec_ws))) ? 1 : 0;
-  dim3 grid(p.tiles_m * p.tiles_n * p.splits, 1, batch);
-  if (cfg == 2) {
-    if (opts && opts->pf_ptr && opts->pf_bytes > 0) {   // this launch's operand prefetch
-      p.pf_ptr = (const char*)opts->pf_ptr;
-      p.pf_bytes = opts->pf_bytes;
-    }
-    // the 32x32x16 main loop stores from registers only (store_direct_8ph32): launches that need the LDS-staged
-    // epilogue (C += A.B^T, a per-element bias, unaligned C) stay on the 16x16x32 loop
-    const int mf = opts ? opts->mfma : 0;
-    // only where the separate reducer would be the plain one (same summation order: bit-identical results); narrow
-    // outputs with many splits keep splitk_reduce_wide_kernel
-    const long long fx_blocks = ((long long)M * N / 4 + 255) / 256;
-    if (opts && opts->fixup && opts->fx_state && p.splits > 1 && p.splits <= 32 && p.direct_epi && p.vec_ws &&
-        batch == 1 && !(mf == 32) && !(p.splits >= 8 && fx_blocks < 512)) {
-      p.fixup = 1;
-      p.fx_cnt = opts->fx_state;
-      p.fx_dep = opts->fx_state + p.tiles_m * p.tiles_n;
-    }
-    if (p.fixup)
-      hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<3>, grid, dim3(512), 0, stream, p);
-    else if (mf == 32 && p.direct_epi)
-      hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph32_kernel, grid, dim3(512), 0, stream, p);
-    else
+  p.seg_k = seg_k; p.seg_stride_b = seg_stride_b;
+  p.tiles_m = plan.tiles_m; p.tiles_n = plan.tiles_n;
+  p.vec_ws = plan.vec_ws; p.vec_c = plan.vec_c; p.direct_epi = plan.direct_epi;
+  if (plan.cfg == 2 && opts && opts->pf_ptr && opts->pf_bytes > 0) {   // this launch's operand prefetch (8-phase only)
+    p.pf_ptr = (const char*)opts->pf_ptr;
+    p.pf_bytes = opts->pf_bytes;
+  }
+  if (plan.kernel == nsdb::GEMM_8PH_FIXUP) {
+    p.fixup = 1;
+    p.fx_cnt = opts->fx_state;
+    p.fx_dep = opts->fx_state + plan.tiles_m * plan.tiles_n;
+  }
+  // 3. the planned kernel, then the planned reducer
+  const dim3 grid(plan.tiles_m * plan.tiles_n * plan.splits, 1, batch);
+  const bool ki = plan.kinter != 0;
+  switch (plan.kernel) {
+    case nsdb::GEMM_TILE128:
+      hipLaunchKernelGGL((nsdb::gemm_nt_tile_kernel<128, 128, 2, 2>), grid, dim3(256), 0, stream, p);
+      break;
+    case nsdb::GEMM_8PH:
       hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<0>, grid, dim3(512), 0, stream, p);
-  } else if (cfg == 3 || cfg == 4) {
-    // contiguous K chunks per split; k-interleaved splits on request (GemmOpts::kinter, unsegmented B only: a split
-    // must stay inside one segment). A/B in profiles/r5_stream: interleaving wins 3 % at M = 1000, N <= 128 and
-    // loses 4-5 % on the batched dedup panels, so it is not the default.
-    const bool ki = seg_k == 0 && p.splits > 1 && opts && opts->kinter;
-    if (cfg == 3) {
+      break;
+    case nsdb::GEMM_8PH32:
+      hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph32_kernel, grid, dim3(512), 0, stream, p);
+      break;
+    case nsdb::GEMM_8PH_FIXUP:
+      hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<3>, grid, dim3(512), 0, stream, p);
+      break;
+    case nsdb::GEMM_STREAM256X128:
       if (ki) hipLaunchKernelGGL((nsdb::gemm_nt_stream_kernel<256, 128, 4, 2, 3, true>), grid, dim3(512), 0, stream, p);
       else hipLaunchKernelGGL((nsdb::gemm_nt_stream_kernel<256, 128, 4, 2, 3, false>), grid, dim3(512), 0, stream, p);
-    } else {
+      break;
+    case nsdb::GEMM_STREAM128X256:
       if (ki) hipLaunchKernelGGL((nsdb::gemm_nt_stream_kernel<128, 256, 2, 4, 3, true>), grid, dim3(512), 0, stream, p);
       else hipLaunchKernelGGL((nsdb::gemm_nt_stream_kernel<128, 256, 2, 4, 3, false>), grid, dim3(512), 0, stream, p);
-    }
-  } else {
-    hipLaunchKernelGGL((nsdb::gemm_nt_tile_kernel<128, 128, 2, 2>), grid, dim3(256), 0, stream, p);
+      break;
   }
-  if (p.splits > 1 && !p.fixup) {
-    const long long MN = (long long)M * N;
-    const long long plain_blocks = ((p.vec_ws ? MN / 4 : MN) + 255) / 256;
-    if (p.vec_ws && p.splits >= 8 && plain_blocks * batch < 512) {
-      hipLaunchKernelGGL(nsdb::splitk_reduce_wide_kernel, dim3((unsigned)((MN / 4 + 63) / 64), batch), dim3(512), 0,
-                         stream, p);
-    } else {
-      int blocks = (int)std::min<long long>(plain_blocks, 4096);
-      hipLaunchKernelGGL(nsdb::splitk_reduce_kernel, dim3(blocks, batch), dim3(256), 0, stream, p);
-    }
+  switch (plan.reducer) {
+    case nsdb::GEMM_REDUCE_PLAIN:
+      hipLaunchKernelGGL(nsdb::splitk_reduce_kernel, dim3(plan.reduce_blocks, batch), dim3(256), 0, stream, p);
+      break;
+    case nsdb::GEMM_REDUCE_WIDE:
+      hipLaunchKernelGGL(nsdb::splitk_reduce_wide_kernel, dim3(plan.reduce_blocks, batch), dim3(512), 0, stream, p);
+      break;
+    default:                  // unsplit, or reduced inside the launch
+      break;
   }
   return (int)hipGetLastError();
 }

@@ -3,11 +3,11 @@
 // split-K reducer epilogue. Reference pattern: src/FF/headers/FFTransposeMult.h + FFAggMatrix.h.
 #pragma once
 #include "common.h"
+#include "gemm_plan.h"      // BM, BN, BK and the launch plan (host arithmetic)
 #include <algorithm>
 
 namespace nsdb {
 
-constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int NTHREADS = 256;
 constexpr int TILE_BYTES = BM * BK * 2;          // 16 KiB per operand per stage
 constexpr int STAGE_BYTES = 2 * TILE_BYTES;      // A + B

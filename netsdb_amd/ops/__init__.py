@@ -115,20 +115,18 @@ def gemm_nt(A, B, bias=None, bias_mode=BIAS_NONE, act=ACT_NONE, out_dtype=torch.
         if bias is not None and bias.dtype != torch.float32:
             bias = bias.float()
         A, B = gemm_operands(A, B)
-        h = _ext.hip()
-        c = -1 if cfg is None else int(cfg)
         pf = None
         streams = _streams()
         if streams._armed_pf:
-            M, N, K = A.shape[-2], B.shape[-2], A.shape[-1]
             batch = A.shape[0] if A.dim() == 3 else 1
-            if h.gemm_prefetch_eligible(M, N, K, batch, int(splits), c):
+            if gemm_plan(A.shape[-2], B.shape[-2], A.shape[-1], batch, splits, cfg)["prefetch_eligible"]:
                 pf = streams.take_operand_prefetch(A.device)
-        return h.gemm_nt(A, B, bias, int(bias_mode if bias is not None else 0), act,
-                         out_dtype == torch.float32, float(alpha), float(dropout), int(seed),
-                         int(splits), out, bool(accumulate), c, -1 if epi is None else int(epi), pf,
-                         int(mfma if mfma is not None else _kopt("gemm_mfma", 0)),
-                         int(fixup if fixup is not None else _kopt("gemm_fixup", 0)))
+        return _ext.hip().gemm_nt(A, B, bias, int(bias_mode if bias is not None else 0), act,
+                                  out_dtype == torch.float32, float(alpha), float(dropout), int(seed),
+                                  int(splits), out, bool(accumulate), -1 if cfg is None else int(cfg),
+                                  -1 if epi is None else int(epi), pf,
+                                  int(mfma if mfma is not None else _kopt("gemm_mfma", 0)),
+                                  int(fixup if fixup is not None else _kopt("gemm_fixup", 0)))
     v = torch.matmul(A.float(), B.float().transpose(-1, -2)) * alpha
     if bias is not None:
         b = bias.float()
@@ -232,6 +230,22 @@ def gemm_nt_segmented(A, Bg, bias=None, bias_mode=BIAS_NONE, act=ACT_NONE, out_d
 
 def gemm_splits(M, N, K, batch=1) -> int:
     return int(_ext.hip().gemm_splits(M, N, K, batch))
+
+
+def gemm_plan(M, N, K, batch=1, splits=0, cfg=None, epi=None, mfma=None, fixup=None, out_dtype=torch.bfloat16,
+              accumulate=False, bias_mode=BIAS_NONE, ldc=None, c_align=16, seg_k=0) -> dict:
+    """What a GPU ``gemm_nt`` call of this shape and these options becomes (the options are requests): ``kernel``
+    ("tile128", "8ph", "8ph32", "8ph_fixup", "stream256x128", "stream128x256"), ``cfg``, the effective ``splits``,
+    ``reducer`` ("none", "plain", "wide", "in_launch"), ``direct_epi``, ``kinter``, ``wgs`` and ``prefetch_eligible``.
+    Host arithmetic only: the function of gemm_plan.h that the launch itself follows. ``mfma`` / ``fixup`` None take the
+    calling thread's ``kernel_options``, as in ``gemm_nt``; ``ldc`` is C's row stride (default N), ``c_align`` the
+    alignment of its address in bytes, ``seg_k`` the segment length of ``gemm_nt_segmented``'s B."""
+    return _ext.hip().gemm_plan(int(M), int(N), int(K), int(batch), int(splits), -1 if cfg is None else int(cfg),
+                                -1 if epi is None else int(epi),
+                                int(mfma if mfma is not None else _kopt("gemm_mfma", 0)),
+                                int(fixup if fixup is not None else _kopt("gemm_fixup", 0)),
+                                out_dtype == torch.float32, bool(accumulate), int(bias_mode),
+                                -1 if ldc is None else int(ldc), int(c_align), int(seg_k))
 
 
 _DERIVED: "OrderedDict" = None

@@ -36,10 +36,25 @@ def gemm_cfg(request):
     return request.param
 
 
+CFG_KERNEL = {0: "tile128", 2: "8ph", 3: "stream256x128", 4: "stream128x256"}
+
+
+def _cfg_plan(gemm_cfg, M, N, K, **kw):
+    """The plan (ops.gemm_plan) of a gemm_nt call on the fixture's config with default mfma / fixup: the forced config
+    is the one that runs, on that config's plain kernel."""
+    plan = ops.gemm_plan(M, N, K, cfg=gemm_cfg, **kw)
+    assert gemm_cfg is None or plan["cfg"] == gemm_cfg
+    assert plan["kernel"] == CFG_KERNEL[plan["cfg"]] and not plan["kinter"]
+    return plan
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (1000, 1000, 4096), (77, 300, 520), (513, 129, 8), (2048, 64, 1024),
                                    (600, 520, 2056), (256, 256, 64), (1024, 768, 8192), (300, 1000, 576)])
 @pytest.mark.parametrize("splits", [0, 1, 3])
 def test_gemm_shapes(M, N, K, splits, gemm_cfg):
+    plan = _cfg_plan(gemm_cfg, M, N, K, splits=splits, out_dtype=torch.float32)
+    assert plan["splits"] == min(splits, (K + 63) // 64) or splits == 0
+    assert (plan["reducer"] == "none") == (plan["splits"] == 1)
     torch.manual_seed(0)
     A = torch.randn(M, K, device=DEV).to(torch.bfloat16)
     B = torch.randn(N, K, device=DEV).to(torch.bfloat16)
@@ -52,6 +67,8 @@ def test_gemm_shapes(M, N, K, splits, gemm_cfg):
 def test_gemm_epilogue(mode, act, splits, gemm_cfg):
     torch.manual_seed(1)
     M, N, K = 300, 200, 640
+    for dt in (torch.float32, torch.bfloat16):
+        assert _cfg_plan(gemm_cfg, M, N, K, splits=splits, bias_mode=mode, out_dtype=dt)["splits"] == splits
     A = (torch.randn(M, K, device=DEV) * 0.05).to(torch.bfloat16)
     B = (torch.randn(N, K, device=DEV) * 0.05).to(torch.bfloat16)
     bias = torch.randn(M if mode == 1 else N, device=DEV)
@@ -61,14 +78,22 @@ def test_gemm_epilogue(mode, act, splits, gemm_cfg):
     _close(Cb, _ref_gemm(A, B, bias, mode, act), tol=2e-2)
 
 
-@pytest.mark.parametrize("M,N,K", [(300, 200, 640), (1000, 1030, 1000), (257, 514, 64)])
+@pytest.mark.parametrize("M,N,K", [(300, 200, 640), (1000, 1030, 1000), (257, 514, 64), (1000, 1032, 1000),
+                                   (257, 516, 64)])
 @pytest.mark.parametrize("mode,act,dropout", [(0, ops.ACT_NONE, 0.0), (1, ops.ACT_RELU, 0.0), (2, ops.ACT_EXP, 0.0),
                                               (2, ops.ACT_SIGMOID, 0.3)])
 @pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
 def test_gemm_8ph_direct_epilogue_matches_lds_staged(M, N, K, mode, act, dropout, out_dtype):
     """The 8-phase kernel's direct register epilogue (epi=1, default for unsplit launches) and its LDS-staged
     epilogue (epi=0) write the same values (same fp32 math, same dropout hash), ragged edges included; both
-    against the fp32 reference."""
+    against the fp32 reference. The direct epilogue needs C rows that take 4-column vector stores: with a contiguous
+    C the N % 4 != 0 shapes (1030, 514) stay LDS-staged under epi=1 too and reach the direct stores only through the
+    ldc-padded view below; N = 1032 and 516 (still ragged on both tile edges) reach them in both forms."""
+    pk = dict(cfg=2, splits=1, bias_mode=mode, out_dtype=out_dtype)
+    assert ops.gemm_plan(M, N, K, epi=1, **pk) == dict(ops.gemm_plan(M, N, K, **pk), direct_epi=N % 4 == 0)
+    assert ops.gemm_plan(M, N, K, epi=1, ldc=(N + 63) // 64 * 64, **pk)["direct_epi"]
+    staged = ops.gemm_plan(M, N, K, epi=0, **pk)
+    assert staged["kernel"] == "8ph" and not staged["direct_epi"] and staged["splits"] == 1
     torch.manual_seed(7)
     A = (torch.randn(M, K, device=DEV) * 0.05).to(torch.bfloat16)
     B = (torch.randn(N, K, device=DEV) * 0.05).to(torch.bfloat16)
@@ -91,6 +116,7 @@ def test_gemm_8ph_mfma32_identity_asymmetric():
     """The 32x32x16 main loop (mfma=32): A = I with an asymmetric B catches a transposed C-write or a wrong k
     permutation between the two operands' fragments."""
     n = 512
+    assert ops.gemm_plan(n, n, n, cfg=2, splits=1, mfma=32, out_dtype=torch.float32)["kernel"] == "8ph32"
     A = torch.eye(n, device=DEV, dtype=torch.bfloat16)
     B = (torch.arange(n * n, device=DEV, dtype=torch.float32).reshape(n, n) % 97 - 48).to(torch.bfloat16)
     C = ops.gemm_nt(A, B, out_dtype=torch.float32, cfg=2, splits=1, mfma=32)
@@ -100,11 +126,17 @@ def test_gemm_8ph_mfma32_identity_asymmetric():
 
 
 @pytest.mark.parametrize("M,N,K", [(1000, 1000, 6400), (300, 200, 640), (1000, 1030, 1000), (257, 514, 72),
-                                   (256, 256, 64), (513, 260, 8200)])
+                                   (256, 256, 64), (513, 260, 8200), (1000, 1032, 1000), (257, 516, 72)])
 @pytest.mark.parametrize("splits", [1, 3, 16])
 def test_gemm_8ph_mfma32_exact_vs_mfma16(M, N, K, splits):
     """Small-integer operands make every partial sum exact in f32, so the 32x32x16 and 16x16x32 main loops must
-    agree bit for bit (split-K slabs + reducer, ragged M / N / K edges), and both equal the f32 reference."""
+    agree bit for bit (split-K slabs + reducer, ragged M / N / K edges), and both equal the f32 reference. The
+    32x32x16 loop stores from registers only, in 4-column vectors: N = 1030 and 514 (N % 4 != 0) run the 16x16x32
+    loop under mfma=32 too; 1032 and 516 are their nearest shapes that reach it."""
+    pk = dict(cfg=2, splits=splits, out_dtype=torch.float32)
+    p32, p16 = ops.gemm_plan(M, N, K, mfma=32, **pk), ops.gemm_plan(M, N, K, mfma=16, **pk)
+    assert p32["kernel"] == ("8ph32" if N % 4 == 0 else "8ph") and p16["kernel"] == "8ph"
+    assert {**p32, "kernel": "8ph"} == p16                  # the same splits, reducer and epilogue form otherwise
     torch.manual_seed(21)
     A = torch.randint(-3, 4, (M, K), device=DEV).to(torch.bfloat16)
     B = torch.randint(-3, 4, (N, K), device=DEV).to(torch.bfloat16)
@@ -114,15 +146,38 @@ def test_gemm_8ph_mfma32_exact_vs_mfma16(M, N, K, splits):
     torch.testing.assert_close(c32, _ref_gemm(A, B), rtol=0, atol=0)
 
 
-@pytest.mark.parametrize("mode,act,dropout", [(0, ops.ACT_NONE, 0.0), (1, ops.ACT_RELU, 0.0), (2, ops.ACT_EXP, 0.0),
-                                              (2, ops.ACT_SIGMOID, 0.3), (1, ops.ACT_RELU, 0.5)])
-@pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("splits", [1, 4])
+def _mfma32_epilogue_cases(f):
+    """The epilogue cases shared by test_gemm_8ph_mfma32_epilogue and its N = 1032 twin."""
+    f = pytest.mark.parametrize("splits", [1, 4])(f)
+    f = pytest.mark.parametrize("out_dtype", [torch.float32, torch.bfloat16])(f)
+    return pytest.mark.parametrize("mode,act,dropout", [(0, ops.ACT_NONE, 0.0), (1, ops.ACT_RELU, 0.0),
+                                                        (2, ops.ACT_EXP, 0.0), (2, ops.ACT_SIGMOID, 0.3),
+                                                        (1, ops.ACT_RELU, 0.5)])(f)
+
+
+@_mfma32_epilogue_cases
 def test_gemm_8ph_mfma32_epilogue(mode, act, dropout, out_dtype, splits):
     """The 32x32x16 loop's register epilogue (bias per row / column, activations, dropout hash, bf16 packing) and
-    its split-K slabs against the fp32 reference, with the dropout mask equal to the 16x16x32 loop's."""
+    its split-K slabs against the fp32 reference, with the dropout mask equal to the 16x16x32 loop's — as requested:
+    at N = 1030 neither C rows nor slabs take 4-column vector stores, so mfma=32 runs the 16x16x32 loop here and the
+    two arms are one kernel. test_gemm_8ph_mfma32_epilogue_vector_rows is the shape that runs the 32x32x16 loop."""
+    _mfma32_epilogue(1030, "8ph", mode, act, dropout, out_dtype, splits)
+
+
+@_mfma32_epilogue_cases
+def test_gemm_8ph_mfma32_epilogue_vector_rows(mode, act, dropout, out_dtype, splits):
+    """test_gemm_8ph_mfma32_epilogue at N = 1032 (still ragged on both tile edges): the 32x32x16 loop and its register
+    epilogue run."""
+    _mfma32_epilogue(1032, "8ph32", mode, act, dropout, out_dtype, splits)
+
+
+def _mfma32_epilogue(N, kernel32, mode, act, dropout, out_dtype, splits):
+    M, K = 1000, 1024
+    pk = dict(cfg=2, splits=splits, bias_mode=mode, out_dtype=out_dtype)
+    p32 = ops.gemm_plan(M, N, K, mfma=32, **pk)
+    assert p32["kernel"] == kernel32 and p32["splits"] == splits
+    assert ops.gemm_plan(M, N, K, mfma=16, **pk) == {**p32, "kernel": "8ph"}
     torch.manual_seed(8)
-    M, N, K = 1000, 1030, 1024
     A = (torch.randn(M, K, device=DEV) * 0.05).to(torch.bfloat16)
     B = (torch.randn(N, K, device=DEV) * 0.05).to(torch.bfloat16)
     bias = torch.randn(M if mode == 1 else N, device=DEV) if mode else None
@@ -139,6 +194,8 @@ def test_gemm_8ph_mfma32_ff_layer1_shape():
     """The headline layer-1 shape class (M = N = 1000, K long, split-K 16) on the 32x32x16 loop vs fp32."""
     torch.manual_seed(9)
     M, N, K = 1000, 1000, 65536
+    plan = ops.gemm_plan(M, N, K, cfg=2, mfma=32, out_dtype=torch.float32)
+    assert (plan["kernel"], plan["splits"], plan["reducer"], plan["wgs"]) == ("8ph32", 16, "plain", 256)
     A = (torch.rand(M, K, device=DEV) - 0.5).to(torch.bfloat16)
     B = (torch.rand(N, K, device=DEV) - 0.5).to(torch.bfloat16)
     C = ops.gemm_nt(A, B, out_dtype=torch.float32, cfg=2, mfma=32)
@@ -153,6 +210,12 @@ def test_gemm_8ph_split_k_fixup_bit_exact(M, N, K, splits, out_dtype):
     to the separate reducer — the same slabs summed in split order, the same epilogue (bias, relu, dropout) — on
     ragged M / N edges, three launches in a row (the arrival / departure words are re-zeroed by each launch). Narrow
     outputs with many splits (300 x 1028 at 32) keep the wide reducer: equal by construction there."""
+    narrow = (M, N) == (300, 1028)
+    pk = dict(cfg=2, splits=splits, bias_mode=ops.BIAS_COL, out_dtype=out_dtype)
+    fixed, sep = ops.gemm_plan(M, N, K, fixup=1, **pk), ops.gemm_plan(M, N, K, fixup=0, **pk)
+    assert (sep["kernel"], sep["reducer"], sep["splits"]) == ("8ph", "wide" if narrow else "plain", splits)
+    assert fixed == (sep if narrow else {**sep, "kernel": "8ph_fixup", "reducer": "in_launch"})
+    assert ops.gemm_plan(M, N, K, fixup=1, cfg=2, splits=splits, out_dtype=torch.float32)["kernel"] == fixed["kernel"]
     torch.manual_seed(13)
     A = (torch.rand(M, K, device=DEV) - 0.5).to(torch.bfloat16)
     B = (torch.rand(N, K, device=DEV) - 0.5).to(torch.bfloat16)
@@ -167,6 +230,7 @@ def test_gemm_8ph_split_k_fixup_bit_exact(M, N, K, splits, out_dtype):
 
 
 def test_gemm_batched_strided(gemm_cfg):
+    _cfg_plan(gemm_cfg, 130, 70, 192, batch=3, out_dtype=torch.float32)
     torch.manual_seed(2)
     A = torch.randn(3, 130, 200, device=DEV).to(torch.bfloat16)[:, :, :192]   # row stride 200 > K
     B = torch.randn(3, 70, 192, device=DEV).to(torch.bfloat16)
@@ -180,6 +244,14 @@ def test_gemm_batched_strided(gemm_cfg):
 def test_gemm_stream_skinny_long_k(M, N, K, batch):
     """The skinny long-K stream tiles (cfg 3: 256x128, cfg 4: 128x256; the dedup scoring shapes, scaled down)
     against the fp32 reference and bit-exact against each other's split partition: same k-tiles, same order."""
+    for cfg, kernel in ((3, "stream256x128"), (4, "stream128x256"), (5, "stream256x128"), (6, "stream128x256")):
+        plan = ops.gemm_plan(M, N, K, batch, cfg=cfg, out_dtype=torch.float32)
+        # every shape here splits K, so cfg 5 / 6 do run the k-interleaved instantiation
+        assert plan["kernel"] == kernel and plan["splits"] > 1 and plan["kinter"] == (cfg >= 5)
+    # auto takes the stream tile of the long side from 256 k-tiles (K >= 16384) on; below that (500 x 100 x 10000)
+    # the 128x128 tile
+    auto = "tile128" if K < 16384 else "stream256x128" if M > N else "stream128x256"
+    assert ops.gemm_plan(M, N, K, batch, out_dtype=torch.float32)["kernel"] == auto
     torch.manual_seed(11)
     shp = (batch,) if batch > 1 else ()
     A = (torch.rand(*shp, M, K, device=DEV) - 0.5).to(torch.bfloat16)
@@ -191,6 +263,8 @@ def test_gemm_stream_skinny_long_k(M, N, K, batch):
 
 
 def test_gemm_accumulate(gemm_cfg):
+    # C += A.B^T goes through the LDS-staged epilogue on every config
+    assert not _cfg_plan(gemm_cfg, 300, 280, 256, accumulate=True, out_dtype=torch.float32)["direct_epi"]
     torch.manual_seed(5)
     A = torch.randn(300, 256, device=DEV).to(torch.bfloat16)
     B = torch.randn(280, 256, device=DEV).to(torch.bfloat16)
@@ -311,6 +385,14 @@ def test_gemm_segmented_b_in_place(S, N, segk, M, out_f32):
     _close(C, ref, tol=1e-2 if out_f32 else 2e-2)
 
 
+def test_gemm_segmented_rejects_a_host_bias():
+    """A CPU bias with GPU operands would hand the kernel a host pointer: the binding refuses before any launch."""
+    A = torch.zeros(64, 128, device=DEV, dtype=torch.bfloat16)
+    Bg = torch.zeros(2, 32, 64, device=DEV, dtype=torch.bfloat16)
+    with pytest.raises(RuntimeError, match="bias must be a GPU tensor"):
+        ops.gemm_nt_segmented(A, Bg, torch.zeros(32), ops.BIAS_COL)
+
+
 def test_gemm_bias_matrix_epilogue():
     torch.manual_seed(10)
     A = torch.randn(300, 256, device=DEV).to(torch.bfloat16)
@@ -335,6 +417,8 @@ def test_gemm_narrow_many_splits_wide_reducer(M, N, K):
     A = (torch.randn(M, K, device="cuda:0", generator=g) * 0.05).to(torch.bfloat16)
     B = (torch.randn(N, K, device="cuda:0", generator=g) * 0.05).to(torch.bfloat16)
     assert ops.gemm_splits(M, N, K) >= 8
+    plan = ops.gemm_plan(M, N, K, bias_mode=ops.BIAS_MAT, out_dtype=torch.float32)
+    assert plan["reducer"] == "wide" and plan["splits"] == ops.gemm_splits(M, N, K)
     bias = torch.randn(M, N, device="cuda:0")
     C = ops.gemm_nt(A, B, bias, ops.BIAS_MAT, out_dtype=torch.float32)
     ref = A.float() @ B.float().t() + bias
