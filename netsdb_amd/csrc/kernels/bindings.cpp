@@ -25,6 +25,7 @@ int nsdb_gemm_nt_softmax(const void* A, const void* B, float* C, const float* bi
                          long long ldb, long long ldc, int bias_mode, float alpha, int axis, void* part, int* cnt,
                          int* flag, int* dep, int force_fallback, int epi, unsigned long long* stamps,
                          hipStream_t stream);
+int nsdb_pack_ktile(const void* src, void* out, int rows, int K, long long ld, hipStream_t stream);
 int nsdb_gemm_nt_f32(const float* A, const float* B, float* C, int M, int N, int K, long long lda, long long ldb,
                      long long ldc, float alpha, int accumulate, hipStream_t stream);
 struct ConvOpts {
@@ -96,6 +97,8 @@ struct GemmOpts {
   int mfma;
   int fixup;
   int* fx_state;
+  int packed;
+  const void* pk_ptr;
 };
 
 torch::Tensor softmax_state(const torch::Tensor& like, int64_t need, hipStream_t st);
@@ -134,7 +137,8 @@ int take_kinter(int64_t& cfg) {
 torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Tensor> bias, int64_t bias_mode,
                       int64_t act, bool out_f32, double alpha, double dropout, int64_t seed, int64_t splits,
                       c10::optional<torch::Tensor> out, bool accumulate, int64_t cfg, int64_t epi,
-                      c10::optional<torch::Tensor> prefetch, int64_t mfma, int64_t fixup) {
+                      c10::optional<torch::Tensor> prefetch, int64_t mfma, int64_t fixup,
+                      c10::optional<torch::Tensor> a_packed, c10::optional<torch::Tensor> b_packed) {
   check_cuda(A, "A");
   check_cuda(B, "B");
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && B.scalar_type() == torch::kBFloat16, "A,B must be bf16");
@@ -191,6 +195,19 @@ torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Ten
   call.ldc = C.defined() ? C.stride(-2) : N;
   call.sC = !batched ? 0 : C.defined() ? C.stride(0) : M * N;
   call.c_align = C.defined() ? nsdb::gemm_ptr_align(C.data_ptr()) : 16;
+  // a k-tile-major copy of A or of B (pack_ktile; A's when both are given): a request, the plan says whether the
+  // launch streams it
+  const bool has_pa = a_packed.has_value() && a_packed->defined();
+  const bool has_pb = b_packed.has_value() && b_packed->defined();
+  const torch::Tensor* pk = has_pa ? &*a_packed : has_pb ? &*b_packed : nullptr;
+  if (pk) {
+    const int64_t rows = has_pa ? M : N;
+    check_same_device(*pk, A, "a_packed / b_packed");
+    TORCH_CHECK(!batched && pk->scalar_type() == torch::kBFloat16 && pk->is_contiguous() && pk->dim() == 3 &&
+                    pk->size(0) == (K + 63) / 64 && pk->size(1) == nsdb::packed_rows(rows) && pk->size(2) == 64,
+                "gemm_nt: a packed operand must be pack_ktile of that 2-D operand: [ceil(K/64), roundup(rows, 256), 64] bf16");
+    call.packed = has_pa ? 1 : 2;
+  }
   const nsdb::GemmPlan plan = nsdb::gemm_plan(call);
   check_rc(plan.rc, "gemm_nt");
   if (!C.defined()) C = batched ? torch::empty({batch, M, N}, opts) : torch::empty({M, N}, opts);
@@ -200,7 +217,7 @@ torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B, c10::optional<torch::Ten
     ws = torch::empty({batch * plan.splits * M * N}, A.options().dtype(torch::kFloat32));
     wsp = ws.data_ptr<float>();
   }
-  GemmOpts o{(int)cfg, (int)epi, nullptr, 0, kinter, (int)mfma, 0, nullptr};
+  GemmOpts o{(int)cfg, (int)epi, nullptr, 0, kinter, (int)mfma, 0, nullptr, call.packed, pk ? pk->data_ptr() : nullptr};
   if (plan.kernel == nsdb::GEMM_8PH_FIXUP) {
     // the in-launch split-K reduction's arrival / departure words: zero between launches on this stream (shared
     // with the fused softmax's, which also leaves them zero)
@@ -388,7 +405,7 @@ int64_t gemm_splits(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t cfg)
 // C rows of ldc elements (-1: N) at a c_align-byte aligned address (host arithmetic only, no tensors).
 py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t splits, int64_t cfg, int64_t epi, int64_t mfma,
                    int64_t fixup, bool out_f32, bool accumulate, int64_t bias_mode, int64_t ldc, int64_t c_align,
-                   int64_t seg_k) {
+                   int64_t seg_k, int64_t packed) {
   nsdb::GemmCall call;
   call.kinter = take_kinter(cfg);
   call.M = (int)M; call.N = (int)N; call.K = (int)K; call.batch = (int)batch; call.splits = (int)splits;
@@ -398,7 +415,7 @@ py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t split
   call.ldb = seg_k > 0 ? seg_k : K;
   call.ldc = ldc < 0 ? N : ldc;
   call.sC = batch > 1 ? M * call.ldc : 0;
-  call.c_align = (int)c_align; call.seg_k = seg_k;
+  call.c_align = (int)c_align; call.seg_k = seg_k; call.packed = (int)packed;
   const nsdb::GemmPlan p = nsdb::gemm_plan(call);
   check_rc(p.rc, "gemm_plan");
   py::dict d;
@@ -410,7 +427,23 @@ py::dict gemm_plan(int64_t M, int64_t N, int64_t K, int64_t batch, int64_t split
   d["kinter"] = p.kinter != 0;
   d["wgs"] = p.wgs;
   d["prefetch_eligible"] = p.prefetch_eligible != 0;
+  d["packed"] = p.packed;
   return d;
+}
+
+// The k-tile-major packed copy of a 2-D bf16 operand (K-contiguous, 16-B rows): [ceil(K/64)][rows rounded up to
+// 256][64], element [kt][r][c] = t[r][64 kt + c], zero outside rows x K (gemm.hip pack_ktile_kernel).
+torch::Tensor pack_ktile(torch::Tensor t) {
+  check_cuda(t, "t");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16 && t.dim() == 2, "pack_ktile: t must be 2-D bf16");
+  const int64_t rows = t.size(0), K = t.size(1);
+  TORCH_CHECK(rows > 0 && K > 0 && rows < (1LL << 31) && K < (1LL << 31), "pack_ktile: empty or too large");
+  TORCH_CHECK(t.stride(1) == 1 && K % 8 == 0 && t.stride(0) % 8 == 0 && t.stride(0) >= K &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "pack_ktile: t must be K-contiguous with 16-B aligned rows and K % 8 == 0");
+  torch::Tensor out = torch::empty({(K + 63) / 64, nsdb::packed_rows(rows), 64}, t.options());
+  check_rc(nsdb_pack_ktile(t.data_ptr(), out.data_ptr(), (int)rows, (int)K, t.stride(0), cur_stream()), "pack_ktile");
+  return out;
 }
 
 torch::Tensor conv2d(torch::Tensor X, torch::Tensor Wt, c10::optional<torch::Tensor> bias, int64_t KH, int64_t KW,
@@ -842,11 +875,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias_mode") = 0, py::arg("act") = 0, py::arg("out_f32") = false, py::arg("alpha") = 1.0,
         py::arg("dropout") = 0.0, py::arg("seed") = 0, py::arg("splits") = 0, py::arg("out") = py::none(),
         py::arg("accumulate") = false, py::arg("cfg") = -1, py::arg("epi") = -1, py::arg("prefetch") = py::none(),
-        py::arg("mfma") = 0, py::arg("fixup") = 0);
+        py::arg("mfma") = 0, py::arg("fixup") = 0, py::arg("a_packed") = py::none(), py::arg("b_packed") = py::none());
+  m.def("pack_ktile", &pack_ktile, "k-tile-major packed copy of a GEMM operand", py::arg("t"));
   m.def("gemm_plan", &gemm_plan, "the launch plan of a gemm_nt call (host arithmetic only)", py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("batch") = 1, py::arg("splits") = 0, py::arg("cfg") = -1, py::arg("epi") = -1,
         py::arg("mfma") = 0, py::arg("fixup") = 0, py::arg("out_f32") = false, py::arg("accumulate") = false,
-        py::arg("bias_mode") = 0, py::arg("ldc") = -1, py::arg("c_align") = 16, py::arg("seg_k") = 0);
+        py::arg("bias_mode") = 0, py::arg("ldc") = -1, py::arg("c_align") = 16, py::arg("seg_k") = 0,
+        py::arg("packed") = 0);
   m.def("prefetch", &prefetch, "warm the caches with a read of each tensor", py::arg("tensors"), py::arg("sink"),
         py::arg("blocks") = 64);
   m.def("gemm_nt_f32", &gemm_nt_f32, "alpha * A.B^T (+C) on the exact-f32 MFMA (16x16x4)", py::arg("A"),

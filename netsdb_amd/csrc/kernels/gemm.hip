@@ -786,8 +786,15 @@ __global__ void __launch_bounds__(64 * WGM * WGN, 2) gemm_nt_stream_kernel(GemmP
 //  Studies of this loop (diagnostic variants, K-tail stealing, adaptive split-K, in-launch fix-up, ring
 //  buffers, cache policies, the 4-wave structures) live in the separate study build (csrc/study).
 // ---------------------------------------------------------------------------------------------
-template <int EPI>
+//  * PK: 0 = both operands row-major; 1 / 2 = A / B streamed from its k-tile-major packed copy (GemmParams::pk_ptr,
+//    ops.pack_ktile: [k-tile][pk_rows][64], zero-padded), where the 256 rows x 64 k of a tile are one 32 KiB run
+//    instead of 256 lines a row pitch apart. Only stage()'s addressing of that side differs: a loop-invariant
+//    per-lane offset inside the run plus a wave-uniform offset per k-tile, no row or K range tests (the copy is
+//    zero-padded); k-tiles past the split's end take the out-of-range voffset, wave-uniformly. The same VMEM
+//    operations in the same order, the same LDS image, barriers, wait counts and MFMA order: bit-identical results.
+template <int EPI, int PK = 0>
 __global__ void __launch_bounds__(512, 2) gemm_nt_256_8ph_kernel(GemmParams p) {
+  static_assert(PK == 0 || EPI == 0, "packed operands: the common epilogue only");
   // fused-softmax launches may carry diagnostic phase stamps (p.stamps: [tile][8] on the 100 MHz real-time clock)
   constexpr bool SMX = EPI == 1 || EPI == 2;   // the fused-softmax instantiations (EPI 3: split-K, reduced in-launch)
   const unsigned long long t_entry = SMX ? __builtin_amdgcn_s_memrealtime() : 0ull;
@@ -836,7 +843,14 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_256_8ph_kernel(GemmParams p) {
       const int tb = (2 * i + (lr >> 5)) * 64 + q * 32 + (lr & 31);
       roff[q][i] = ta < rows_a ? (int)((long long)ta * p.lda * 2) : -1;
       roff[2 + q][i] = tb < rows_b ? (int)((long long)tb * p.ldb * 2) : -1;
+      if constexpr (PK == 1) roff[q][i] = (ta * BK + kc) * 2;          // inside the tile's 32 KiB run of a k-tile
+      if constexpr (PK == 2) roff[2 + q][i] = (tb * BK + kc) * 2;
     }
+  // packed side: the whole copy is one buffer (< 2^32 - 16 bytes, the plan's condition, so OOB_PK is past its end)
+  constexpr int OOB_PK = (int)0xfffffff0u;
+  const unsigned pk_step = (unsigned)p.pk_rows * 128u;                      // bytes per k-tile of the copy
+  const unsigned pk_base = (unsigned)(kbeg / BK) * pk_step + (unsigned)(PK == 1 ? m0 : n0) * 128u;
+  const __amdgpu_buffer_rsrc_t rp = make_rsrc(p.pk_ptr, (unsigned)((p.K + BK - 1) / BK) * pk_step);
 
   // fused softmax: the tile's per-column (threads 0-255) / per-row (256-511) bias, loaded before the prologue's DMAs
   // and written to LDS after its wait (read by the epilogue, after the main loop's barriers)
@@ -851,6 +865,17 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_256_8ph_kernel(GemmParams p) {
     const int k = kbeg + u * BK + kc;
     const bool kin = k < kend;
     char* dst = smem + buf * BUF + slot * HALF;
+    if constexpr (PK != 0) {
+      if ((PK == 1) == (slot < 2)) {
+        const bool tin = u < nk;                                            // wave-uniform
+        const int soff = tin ? (int)(pk_base + (unsigned)u * pk_step) : 0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (lds_void*)(dst + (i * 64 + wave * 8) * 128), 16,
+                                                   tin ? roff[slot][i] : OOB_PK, soff, 0, 0);
+        return;
+      }
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int ro = roff[slot][i];
@@ -1243,6 +1268,21 @@ __global__ void __launch_bounds__(512, 2) gemm_nt_256_8ph32_kernel(GemmParams p)
   if (p.pf_ptr != nullptr) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// k-tile-major packed copy of a bf16 operand [rows][ld] (K-contiguous): out[kt][r][c] = src[r][64 kt + c], zero
+// outside rows x K, r < rp (rows rounded up to 256). A plain permute, one 16-B chunk per thread on both sides
+// (K % 8 == 0, so a chunk is inside K or outside it); done once per weight (ops.pack_ktile under ops.derived).
+__global__ void __launch_bounds__(256) pack_ktile_kernel(const unsigned short* src, u32x4* out, long long ld, int rows,
+                                                         int K, int rp, long long nchunks) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nchunks) return;
+  const long long rr = i >> 3;
+  const int r = (int)(rr % rp);
+  const int k = (int)(rr / rp) * BK + (int)(i & 7) * 8;
+  u32x4 v = {0u, 0u, 0u, 0u};
+  if (r < rows && k < K) v = *reinterpret_cast<const u32x4*>(src + (long long)r * ld + k);
+  out[i] = v;
+}
+
 
 // Split-K slab reducer + fused epilogue (the ClusterAggregate "combine" of the partial block products).
 __global__ void __launch_bounds__(256) splitk_reduce_kernel(GemmParams p) {
@@ -1338,6 +1378,8 @@ struct GemmOpts {
   int mfma;                 // 8-phase main loop: 0 auto, 16 = 16x16x32, 32 = 32x32x16 (direct epilogue launches)
   int fixup;                // 8-phase split-K: 1 = reduce inside the launch (splitk_fixup_8ph), no reducer launch
   int* fx_state;            // its arrival / departure words ([2 * tiles] ints, zero between launches on a stream)
+  int packed;               // 8-phase: 1 / 2 = pk_ptr is A's / B's k-tile-major copy (pack_ktile); the row-major
+  const void* pk_ptr;       // pointer is passed all the same, and is what the launch reads when the plan drops this
 };
 
 // GemmParams of a plain launch: unsplit, alpha 1, no bias / activation / dropout, no softmax, no diagnostics, every
@@ -1366,6 +1408,18 @@ int nsdb_gemm_splits(int M, int N, int K, int batch, int cfg) { return shape_pla
 // Would a launch of this shape take an operand prefetch (splits <= 0: the launcher's own choice)?
 int nsdb_gemm_prefetch_eligible(int M, int N, int K, int batch, int splits, int cfg) {
   return shape_plan(M, N, K, batch, splits, cfg).prefetch_eligible;
+}
+
+// out ([ceil(K/64)][rows rounded up to 256][64] bf16) = the k-tile-major packed copy of src [rows][ld] (pack_ktile_kernel).
+int nsdb_pack_ktile(const void* src, void* out, int rows, int K, long long ld, hipStream_t stream) {
+  if (rows <= 0 || K <= 0) return 0;
+  if (K % 8 != 0 || ld % 8 != 0 || ld < K) return -1;
+  const long long nchunks = nsdb::packed_bytes(rows, K) / 16;
+  const long long blocks = (nchunks + 255) / 256;
+  if (blocks > 0x7fffffffLL) return -2;
+  hipLaunchKernelGGL(nsdb::pack_ktile_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const unsigned short*)src,
+                     (nsdb::u32x4*)out, ld, rows, K, (int)nsdb::packed_rows(rows), nchunks);
+  return (int)hipGetLastError();
 }
 
 // C (f32) = softmax(alpha * A . B^T + bias) along axis 1 (each row of C) or 2 (each column of C), fused into
@@ -1419,6 +1473,7 @@ int nsdb_gemm_nt_bf16(const void* A, const void* B, void* C, float* ws, const fl
   if (opts) {
     call.cfg = opts->cfg; call.epi = opts->epi; call.mfma = opts->mfma; call.kinter = opts->kinter;
     call.fixup = opts->fixup && opts->fx_state;
+    call.packed = opts->pk_ptr ? opts->packed : 0;
   }
   call.out_f32 = out_f32; call.accumulate = accumulate; call.bias_mode = bias ? bias_mode : 0;
   call.lda = lda; call.ldb = ldb; call.ldc = ldc; call.sC = sC; call.c_align = nsdb::gemm_ptr_align(C);
@@ -1440,6 +1495,10 @@ int nsdb_gemm_nt_bf16(const void* A, const void* B, void* C, float* ws, const fl
     p.pf_ptr = (const char*)opts->pf_ptr;
     p.pf_bytes = opts->pf_bytes;
   }
+  if (plan.kernel == nsdb::GEMM_8PH_PK) {
+    p.pk_ptr = (const unsigned short*)opts->pk_ptr;
+    p.pk_rows = (int)nsdb::packed_rows(plan.packed == 1 ? M : N);
+  }
   if (plan.kernel == nsdb::GEMM_8PH_FIXUP) {
     p.fixup = 1;
     p.fx_cnt = opts->fx_state;
@@ -1454,6 +1513,10 @@ int nsdb_gemm_nt_bf16(const void* A, const void* B, void* C, float* ws, const fl
       break;
     case nsdb::GEMM_8PH:
       hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph_kernel<0>, grid, dim3(512), 0, stream, p);
+      break;
+    case nsdb::GEMM_8PH_PK:
+      if (plan.packed == 1) hipLaunchKernelGGL((nsdb::gemm_nt_256_8ph_kernel<0, 1>), grid, dim3(512), 0, stream, p);
+      else hipLaunchKernelGGL((nsdb::gemm_nt_256_8ph_kernel<0, 2>), grid, dim3(512), 0, stream, p);
       break;
     case nsdb::GEMM_8PH32:
       hipLaunchKernelGGL(nsdb::gemm_nt_256_8ph32_kernel, grid, dim3(512), 0, stream, p);

@@ -65,6 +65,10 @@ struct GemmParams {
   int fixup = 0;
   int* fx_cnt = nullptr;
   int* fx_dep = nullptr;
+  // 8-phase kernel, packed-operand instantiations (plan.packed: 1 = A, 2 = B): that operand's k-tile-major copy
+  // (pack_ktile: [ceil(K/64)][pk_rows][64] bf16, zero outside rows x K; pk_rows = its rows rounded up to 256)
+  const unsigned short* pk_ptr = nullptr;
+  int pk_rows = 0;
 };
 
 // Adaptive split-K partition (8-phase kernel, split-K launches). The splits of one GEMM run on different XCDs

@@ -10,12 +10,14 @@ namespace nsdb {
 constexpr int BM = 128, BN = 128, BK = 64;       // the general tile and the k-tile of every GEMM kernel
 constexpr int BT256 = 256;                       // the 8-phase macro tile (and the long side of the stream tiles)
 
-enum GemmKernel { GEMM_TILE128, GEMM_8PH, GEMM_8PH32, GEMM_8PH_FIXUP, GEMM_STREAM256X128, GEMM_STREAM128X256 };
+enum GemmKernel { GEMM_TILE128, GEMM_8PH, GEMM_8PH32, GEMM_8PH_FIXUP, GEMM_STREAM256X128, GEMM_STREAM128X256,
+                  GEMM_8PH_PK };
 enum GemmReducer { GEMM_REDUCE_NONE, GEMM_REDUCE_PLAIN, GEMM_REDUCE_WIDE, GEMM_REDUCE_IN_LAUNCH };
 
 inline const char* gemm_kernel_name(int k) {
-  static const char* const names[] = {"tile128", "8ph", "8ph32", "8ph_fixup", "stream256x128", "stream128x256"};
-  return k >= 0 && k < 6 ? names[k] : "?";
+  static const char* const names[] = {"tile128", "8ph", "8ph32", "8ph_fixup", "stream256x128", "stream128x256",
+                                      "8ph_pk"};
+  return k >= 0 && k < 7 ? names[k] : "?";
 }
 inline const char* gemm_reducer_name(int r) {
   static const char* const names[] = {"none", "plain", "wide", "in_launch"};
@@ -37,6 +39,7 @@ struct GemmCall {
   int c_align = 16;          // alignment of the C pointer in bytes (gemm_ptr_align)
   long long seg_k = 0;       // K-segmented B: segment length (0: plain B)
   int has_ws = 1;            // a split-K workspace is (or will be) there
+  int packed = 0;            // 8-phase: 1 / 2 = the caller also has A / B as its k-tile-major copy (ops.pack_ktile)
 };
 
 struct GemmPlan {
@@ -53,7 +56,13 @@ struct GemmPlan {
   int reducer = GEMM_REDUCE_NONE;
   int reduce_blocks = 0;     // grid x of the reducer launch (grid y = batch)
   int prefetch_eligible = 0;
+  int packed = 0;            // effective: the operand (1 = A, 2 = B) the launch streams from its packed copy
 };
+
+// Bytes of the k-tile-major packed copy of a [rows, K] operand: [ceil(K / 64)][rows rounded up to 256][64] bf16.
+inline long long packed_rows(long long rows) { return (rows + BT256 - 1) / BT256 * BT256; }
+inline long long packed_bytes(long long rows, long long K) { return (K + BK - 1) / BK * packed_rows(rows) * BK * 2; }
+
 
 // Alignment of a pointer in bytes, as far as the plan cares (16 at most).
 inline int gemm_ptr_align(const void* p) {
@@ -156,6 +165,15 @@ inline GemmPlan gemm_plan(const GemmCall& c) {
     // batched dedup panels, so it is not the default.
     p.kernel = p.cfg == 3 ? GEMM_STREAM256X128 : GEMM_STREAM128X256;
     p.kinter = (c.seg_k == 0 && p.splits > 1 && c.kinter) ? 1 : 0;
+  }
+
+  // A packed operand is streamed only by the plain 16x16x32 8-phase launch (common epilogue, separate reducer) of an
+  // unbatched, unsegmented call, and only when one 32-bit buffer covers the copy with room for the out-of-range
+  // offset behind it; otherwise the request is dropped and the launch reads the row-major operand.
+  if ((c.packed == 1 || c.packed == 2) && p.kernel == GEMM_8PH && p.cfg == 2 && c.mfma != 32 && c.seg_k == 0 &&
+      c.batch == 1 && packed_bytes(c.packed == 1 ? c.M : c.N, c.K) < (1LL << 32) - 16) {
+    p.kernel = GEMM_8PH_PK;
+    p.packed = c.packed;
   }
 
   if (p.kernel == GEMM_8PH_FIXUP) {

@@ -97,7 +97,8 @@ def _streams():
 
 
 def gemm_nt(A, B, bias=None, bias_mode=BIAS_NONE, act=ACT_NONE, out_dtype=torch.bfloat16, alpha=1.0,
-            dropout=0.0, seed=0, splits=0, out=None, accumulate=False, cfg=None, epi=None, mfma=None, fixup=None):
+            dropout=0.0, seed=0, splits=0, out=None, accumulate=False, cfg=None, epi=None, mfma=None, fixup=None,
+            a_packed=None, b_packed=None):
     """epilogue(alpha * A @ B^T) [+ out when accumulate]: A [..,M,K], B [..,N,K] (K-contiguous),
     bias f32 per row/col. ``accumulate`` adds into an existing f32 ``out`` (C += A.B^T). ``cfg`` forces the
     tile config of THIS call (0 = 128x128, 2 = 256x256 8-phase, 3 / 4 = 256x128 / 128x256 skinny long-K stream;
@@ -109,12 +110,20 @@ def gemm_nt(A, B, bias=None, bias_mode=BIAS_NONE, act=ACT_NONE, out_dtype=torch.
     reducer (None = the thread's ``kernel_options(gemm_fixup=...)``, else 0). An operand prefetch armed on
     the current stream (streams.arm_operand_prefetch: a later kernel's operand read into the Infinity Cache by this
     launch's workgroups as they finish) is handed to this launch when it is long enough to take it — per call and
-    per stream, so GEMMs on other lanes or threads never see it."""
+    per stream, so GEMMs on other lanes or threads never see it. ``a_packed`` / ``b_packed`` is ``pack_ktile`` of A / B
+    as passed (a weight's k-tile-major copy, made once): a request like the others, the launch streams that operand from
+    the copy when its plan says ``8ph_pk`` (``gemm_plan(..., packed=1 / 2)``) and reads the row-major one otherwise, with
+    bit-identical results; the CPU path ignores it."""
     act = act_code(act)
     if _use_hip(A, B):
         if bias is not None and bias.dtype != torch.float32:
             bias = bias.float()
+        A0, B0 = A, B
         A, B = gemm_operands(A, B)
+        if A is not A0:         # the copy describes the operand as passed, not a converted or re-padded one
+            a_packed = None
+        if B is not B0:
+            b_packed = None
         pf = None
         streams = _streams()
         if streams._armed_pf:
@@ -126,7 +135,7 @@ def gemm_nt(A, B, bias=None, bias_mode=BIAS_NONE, act=ACT_NONE, out_dtype=torch.
                                   int(splits), out, bool(accumulate), -1 if cfg is None else int(cfg),
                                   -1 if epi is None else int(epi), pf,
                                   int(mfma if mfma is not None else _kopt("gemm_mfma", 0)),
-                                  int(fixup if fixup is not None else _kopt("gemm_fixup", 0)))
+                                  int(fixup if fixup is not None else _kopt("gemm_fixup", 0)), a_packed, b_packed)
     v = torch.matmul(A.float(), B.float().transpose(-1, -2)) * alpha
     if bias is not None:
         b = bias.float()
@@ -233,10 +242,12 @@ def gemm_splits(M, N, K, batch=1) -> int:
 
 
 def gemm_plan(M, N, K, batch=1, splits=0, cfg=None, epi=None, mfma=None, fixup=None, out_dtype=torch.bfloat16,
-              accumulate=False, bias_mode=BIAS_NONE, ldc=None, c_align=16, seg_k=0) -> dict:
+              accumulate=False, bias_mode=BIAS_NONE, ldc=None, c_align=16, seg_k=0, packed=0) -> dict:
     """What a GPU ``gemm_nt`` call of this shape and these options becomes (the options are requests): ``kernel``
-    ("tile128", "8ph", "8ph32", "8ph_fixup", "stream256x128", "stream128x256"), ``cfg``, the effective ``splits``,
-    ``reducer`` ("none", "plain", "wide", "in_launch"), ``direct_epi``, ``kinter``, ``wgs`` and ``prefetch_eligible``.
+    ("tile128", "8ph", "8ph32", "8ph_fixup", "stream256x128", "stream128x256", "8ph_pk"), ``cfg``, the effective ``splits``,
+    ``reducer`` ("none", "plain", "wide", "in_launch"), ``direct_epi``, ``kinter``, ``wgs``, ``prefetch_eligible`` and
+    ``packed`` (the request ``packed`` = 1 / 2, "A / B also comes as its ``pack_ktile`` copy", as the launch honours it:
+    kernel "8ph_pk", or 0 with the plan it has without the request).
     Host arithmetic only: the function of gemm_plan.h that the launch itself follows. ``mfma`` / ``fixup`` None take the
     calling thread's ``kernel_options``, as in ``gemm_nt``; ``ldc`` is C's row stride (default N), ``c_align`` the
     alignment of its address in bytes, ``seg_k`` the segment length of ``gemm_nt_segmented``'s B."""
@@ -245,7 +256,26 @@ def gemm_plan(M, N, K, batch=1, splits=0, cfg=None, epi=None, mfma=None, fixup=N
                                 int(mfma if mfma is not None else _kopt("gemm_mfma", 0)),
                                 int(fixup if fixup is not None else _kopt("gemm_fixup", 0)),
                                 out_dtype == torch.float32, bool(accumulate), int(bias_mode),
-                                -1 if ldc is None else int(ldc), int(c_align), int(seg_k))
+                                -1 if ldc is None else int(ldc), int(c_align), int(seg_k), int(packed))
+
+
+def pack_ktile(t: torch.Tensor) -> torch.Tensor:
+    """The k-tile-major packed copy of a GEMM operand ``t`` [rows, K] (bf16): [ceil(K/64), roundup(rows, 256), 64]
+    with element [kt, r, c] = t[r, 64 kt + c] and zero outside rows x K. The 8-phase GEMM streams a weight from this
+    copy in 32 KiB runs per tile and k-tile (``gemm_nt(..., a_packed= / b_packed=)``) instead of one 128-B line per
+    row; it costs the weight's size again, so it is made once (``derived``)."""
+    rows, K = t.shape
+    if _use_hip(t):
+        if t.dtype != torch.bfloat16:
+            t = t.to(torch.bfloat16)
+        if t.stride(1) != 1 or t.stride(0) % 8 or K % 8:
+            t = pad_k(t.contiguous())
+        if t.data_ptr() % 16:
+            t = t.clone()
+        return _ext.hip().pack_ktile(t)
+    kt, rp = (K + 63) // 64, (rows + 255) // 256 * 256
+    return torch.nn.functional.pad(t.to(torch.bfloat16), (0, kt * 64 - K, 0, rp - rows)).view(rp, kt, 64) \
+        .permute(1, 0, 2).contiguous()
 
 
 _DERIVED: "OrderedDict" = None

@@ -187,6 +187,19 @@ class MatmulNode(Node):
 
         return w.device if arm_operand_prefetch(w) else None
 
+    @staticmethod
+    def _stored_weight(node: Node, t: torch.Tensor) -> bool:
+        """Is the GEMM operand ``t`` a stored model weight read in place: a view of the panel of a scanned set with
+        "model" locality (identical from call to call), on the GPU, bf16 with K-contiguous 16-B rows? Such an
+        operand may be streamed from its k-tile-major copy (ops.pack_ktile, made once under ops.derived: it costs
+        the weight's bytes again). Inputs and intermediates never qualify."""
+        if not isinstance(node, SourceNode) or getattr(node.set, "locality", "job") != "model":
+            return False
+        if not (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0):
+            return False
+        panel = getattr(node.set, "_panel", None)
+        return panel is not None and t.untyped_storage().data_ptr() == panel.untyped_storage().data_ptr()
+
     def _eval(self, engine, A: Dense, B: Dense) -> Dense:
         opA = A.t() if self.p.transpose_a else A           # [M, K]
         opB = B.t() if self.p.transpose_b else B           # [K, N]
@@ -254,12 +267,17 @@ class MatmulNode(Node):
                 phys = ops.gemm_nt_softmax(X, Y, bias_t, mode, axis=axis, out=out) if phys_is_c else \
                     ops.gemm_nt_softmax(Y, X, bias_t, mode, axis=axis, out=out)
                 self.softmax_fused = True
-            elif phys_is_c:
-                phys = ops.gemm_nt(X, Y, bias_t, mode, act, out_dtype=odt, dropout=self.dropout, seed=self.seed,
-                                   out=out)
             else:
-                phys = ops.gemm_nt(Y, X, bias_t, mode, act, out_dtype=odt, dropout=self.dropout, seed=self.seed,
-                                   out=out)
+                P, Q = (X, Y) if phys_is_c else (Y, X)
+                wp, wq = (self.a, self.b) if phys_is_c else (self.b, self.a)
+                pk = {}
+                for side, node, opnd, w in ((1, wp, P, "a_packed"), (2, wq, Q, "b_packed")):
+                    if not pk and self._stored_weight(node, opnd) and ops.gemm_plan(
+                            P.shape[0], Q.shape[0], K8, out_dtype=odt, bias_mode=mode,
+                            ldc=None if out is None else out.stride(0), packed=side)["kernel"] == "8ph_pk":
+                        pk[w] = ops.derived(opnd, "ktile64", ops.pack_ktile)
+                phys = ops.gemm_nt(P, Q, bias_t, mode, act, out_dtype=odt, dropout=self.dropout, seed=self.seed,
+                                   out=out, **pk)
         part, offset, total = None, 0, None
         if opA.part == "rows":
             part, offset, total = "rows", opA.offset, opA.total
