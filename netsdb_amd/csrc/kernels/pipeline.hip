@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(NTHR) pipe_agg_kernel(const PipeArgs a) {
   __shared__ int s_ovf;
   __shared__ unsigned long long s_kept;
   const int tid = threadIdx.x, lane = tid & 63;
-  const double init = a.agg_op == 0 ? 0.0 : (a.agg_op == 1 ? __builtin_inf() : -__builtin_inf());
+  const double init = agg_init(a.agg_op);
   for (int i = tid; i < CAP; i += NTHR) tk[i] = EMPTY;
   for (int i = tid; i < CAP * FMAX; i += NTHR) tv[i] = init;
   if (tid == 0) {
@@ -400,7 +400,7 @@ __global__ void __launch_bounds__(NTHR) pipe_agg_kernel(const PipeArgs a) {
 
 // The global table's initial state (status 0, keys EMPTY, values the aggregation's identity), one launch.
 __global__ void __launch_bounds__(NTHR) pipe_init_kernel(unsigned long long* table, int op) {
-  const double init = op == 0 ? 0.0 : (op == 1 ? __builtin_inf() : -__builtin_inf());
+  const double init = agg_init(op);
   const int i = blockIdx.x * NTHR + threadIdx.x;
   if (i < 2) table[i] = 0;
   if (i < GCAP) table[2 + i] = (u64)EMPTY;
@@ -643,7 +643,7 @@ __global__ void __launch_bounds__(NTHR) tile_agg_kernel(const PipeArgs a) {
   constexpr int KS = F <= 6 ? 2 * KSLOT : KSLOT;   // no register file in VGPRs here: room for more register slots
   const int tid = threadIdx.x, lane = tid & 63;
   u64* regs = reinterpret_cast<u64*>(tile_smem);
-  const double init = a.agg_op == 0 ? 0.0 : (a.agg_op == 1 ? __builtin_inf() : -__builtin_inf());
+  const double init = agg_init(a.agg_op);
   for (int i = tid; i < CAP; i += NTHR) tk[i] = EMPTY;
   for (int i = tid; i < CAP * F; i += NTHR) tv[i] = init;
   if (tid == 0) {

@@ -310,6 +310,57 @@ void choose_tile(PipeArgs& a, int static_bytes, int64_t force, int reg_static_by
   }
 }
 
+// The launch plan of one pipe_agg / pipe_mask call: which kernel form runs and with what geometry. pipe_agg,
+// pipe_mask and pipe_plan all take it from plan_launch, so what pipe_plan reports is what the launchers do.
+//   kmode: 0 register interpreter, 1 LDS-tile, 2 hybrid (LDS-DMA columns), 3 run-time compiled
+//   tile / lds_bytes: rows per tile or DMA block and its dynamic LDS (0 for the register and compiled kernels)
+//   rows: rows per thread and iteration (the register shape: 4 for nreg <= 8, else 2; tile / 256; the compiled ROWS)
+//   F: the value-count instantiation (2, 4, 6, 8) of the ahead-of-time aggregates; 0 for a mask or a compiled kernel
+//   nwg: workgroups launched (0: a mask over no rows launches nothing)
+// kmode, tile and lds_bytes travel to the kernels in the argument image and nwg is the launch's grid, so those cannot
+// differ from the launch. rows and F of the ahead-of-time kernels are MIRRORED here: pipeline.hip picks the template
+// instantiation itself (nsdb_pipe_agg / nsdb_pipe_mask / launch_agg: NREG_SMALL x 4 rows when a.nreg <= NREG_SMALL,
+// else NREG x 2; F = 2, 4, 6, 8 from a.nval) from the same a.nreg / a.nval by the same rule. Change both together.
+constexpr int KM_JIT = 3;
+struct LaunchPlan {
+  int kmode, tile, lds_bytes, nreg, rows, F, nwg;
+};
+
+// Decides the form for the filled argument image `a` and finishes the image for it (tile, lds_bytes, kmode, the tile
+// kernels' pre-decoded operands; a mask loads every column up front).
+LaunchPlan plan_launch(PipeArgs& a, bool mask, int64_t max_wg, int64_t tile, int64_t jit, int64_t jit_nreg,
+                       int64_t jit_rows) {
+  const int ROWS = 4, NTHR = sizes(7), CAP = sizes(4);
+  const char* who = mask ? "pipe_mask" : "pipe_agg";
+  LaunchPlan p{0, 0, 0, a.nreg, 0, 0, 0};
+  if (mask)
+    for (int c = 0; c < a.ncol; ++c) a.col[c].late = 0;    // the mask pass loads every column up front
+  const long long cap_wg = mask ? 4096 : (max_wg > 0 ? max_wg : 2048);
+  if (jit != 0) {                                   // the run-time compiled kernel of exactly this program shape
+    TORCH_CHECK(a.nreg == jit_nreg && jit_rows >= 1 && jit_rows <= 16, who, ": compiled kernel for ", jit_nreg,
+                " registers, the program uses ", a.nreg);
+    const long long per = (long long)NTHR * jit_rows * 4;
+    p.kmode = KM_JIT;
+    p.rows = (int)jit_rows;
+    p.nwg = (int)std::max<long long>(1, std::min<long long>(cap_wg, (a.n + per - 1) / per));
+  } else {
+    p.F = mask ? 0 : (a.nval <= 2 ? 2 : (a.nval <= 4 ? 4 : (a.nval <= 6 ? 6 : FMAX)));
+    if (mask) choose_tile(a, 0, tile, 0);
+    else choose_tile(a, CAP * (8 + 8 * p.F) + 16, tile, CAP * (8 + 8 * FMAX) + 16);
+    if (a.kmode == 1) predecode_tile(a);
+    // enough workgroups to fill 256 CUs several times over, each still looping over a few tiles / row blocks
+    const long long per = a.tile ? (long long)a.tile : (long long)NTHR * ROWS * 4;
+    const long long lim = mask ? (a.tile ? 2048 : 4096) : cap_wg;
+    p.kmode = a.kmode;
+    p.tile = a.tile;
+    p.lds_bytes = a.lds_bytes;
+    p.rows = a.kmode == 1 ? a.tile / NTHR : (a.nreg <= sizes(9) ? 4 : 2);
+    p.nwg = (int)std::max<long long>(1, std::min<long long>(lim, (a.n + per - 1) / per));
+  }
+  if (mask && a.n == 0) p.nwg = 0;
+  return p;
+}
+
 // ---- run-time compiled kernels (pipeline_core.h jit_agg_body / jit_mask_body; sources from execution/pipeline.py)
 // hiprtc compile of one generated source whose only include is pipeline_core.h (passed as text): the gfx950 code
 // object, with the flags of the ahead-of-time kernels (-O3, hardware float atomics).
@@ -366,7 +417,7 @@ torch::Tensor pipe_agg(torch::Tensor prog, int64_t nins_a, ColList cols, torch::
                        std::vector<int64_t> kpool, int64_t jit, int64_t jit_nreg, int64_t jit_rows,
                        c10::optional<torch::Tensor> jtab, c10::optional<torch::Tensor> jperm, int64_t bn,
                        c10::optional<torch::Tensor> jbloom) {
-  const int ROWS = 4, NTHR = sizes(7), GCAP = sizes(8), CAP = sizes(4);
+  const int NTHR = sizes(7), GCAP = sizes(8);
   PipeArgs a;
   const bool join = jtab.has_value() && jtab->defined();
   fill_args(a, prog, nins_a, cols, lit, n, keep_reg, key_reg, val_regs, agg_op, kpool, join ? bn : -1);
@@ -388,11 +439,9 @@ torch::Tensor pipe_agg(torch::Tensor prog, int64_t nins_a, ColList cols, torch::
     a.bn = bn;
     set_bloom(a, cap, jbloom, T);
   }
-  if (jit != 0) {                                   // the run-time compiled kernel of exactly this program shape
-    TORCH_CHECK(a.nreg == jit_nreg && jit_rows >= 1 && jit_rows <= 16,
-                "pipe_agg: compiled kernel for ", jit_nreg, " registers, the program uses ", a.nreg);
-    const long long per = (long long)NTHR * jit_rows * 4;
-    const int nwg = (int)std::max<long long>(1, std::min<long long>(max_wg > 0 ? max_wg : 2048, (n + per - 1) / per));
+  const LaunchPlan plan = plan_launch(a, false, max_wg, tile, jit, jit_nreg, jit_rows);
+  const int nwg = plan.nwg;
+  if (plan.kmode == KM_JIT) {
     auto table = torch::empty({2 + (long long)GCAP * (1 + FMAX)}, lit.options().dtype(torch::kInt64));
     a.table = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
     hipStream_t st = c10::hip::getCurrentHIPStream().stream();
@@ -403,12 +452,6 @@ torch::Tensor pipe_agg(torch::Tensor prog, int64_t nins_a, ColList cols, torch::
                 "pipe_agg: compiled kernel launch failed");
     return table;
   }
-  const int F = a.nval <= 2 ? 2 : (a.nval <= 4 ? 4 : (a.nval <= 6 ? 6 : FMAX));
-  choose_tile(a, CAP * (8 + 8 * F) + 16, tile, CAP * (8 + 8 * FMAX) + 16);
-  if (a.kmode == 1) predecode_tile(a);
-  // enough workgroups to fill 256 CUs several times over, each still looping over a few tiles / row blocks
-  const long long per = a.tile ? (long long)a.tile : (long long)NTHR * ROWS * 4;
-  const int nwg = (int)std::max<long long>(1, std::min<long long>(max_wg > 0 ? max_wg : 2048, (n + per - 1) / per));
   auto table = torch::empty({2 + (long long)GCAP * (1 + FMAX)}, lit.options().dtype(torch::kInt64));
   a.table = reinterpret_cast<unsigned long long*>(table.data_ptr<int64_t>());
   const int rc = nsdb_pipe_agg(&a, nwg, c10::hip::getCurrentHIPStream().stream());
@@ -487,35 +530,51 @@ std::vector<torch::Tensor> pipe_emit(torch::Tensor prog, int64_t nins_a, ColList
 // The predicate program's keep flag per row (uint8 [n]); key / values unused.
 torch::Tensor pipe_mask(torch::Tensor prog, ColList cols, torch::Tensor lit, int64_t n, int64_t keep_reg, int64_t tile,
                         std::vector<int64_t> kpool, int64_t jit, int64_t jit_nreg, int64_t jit_rows) {
-  const int ROWS = 4, NTHR = sizes(7);
+  const int NTHR = sizes(7);
   PipeArgs a;
   fill_args(a, prog, prog.size(0), cols, lit, n, keep_reg, -1, {}, 0, kpool);
-  for (int c = 0; c < a.ncol; ++c) a.col[c].late = 0;      // the mask pass loads every column up front
-  if (jit != 0) {
-    TORCH_CHECK(a.nreg == jit_nreg && jit_rows >= 1 && jit_rows <= 16,
-                "pipe_mask: compiled kernel for ", jit_nreg, " registers, the program uses ", a.nreg);
-    auto mask = torch::empty({n}, lit.options().dtype(torch::kUInt8));
-    if (n > 0) {
-      const long long per = (long long)NTHR * jit_rows * 4;
-      const int nwg = (int)std::max<long long>(1, std::min<long long>(4096, (n + per - 1) / per));
-      unsigned char* mp = mask.data_ptr<uint8_t>();
-      void* params[] = {&a, &mp};
-      TORCH_CHECK(hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(jit), nwg, 1, 1, NTHR, 1, 1, 0,
-                                        c10::hip::getCurrentHIPStream().stream(), params, nullptr) == hipSuccess,
-                  "pipe_mask: compiled kernel launch failed");
-    }
+  const LaunchPlan plan = plan_launch(a, true, 0, tile, jit, jit_nreg, jit_rows);
+  auto mask = torch::empty({n}, lit.options().dtype(torch::kUInt8));
+  if (plan.nwg == 0) return mask;
+  if (plan.kmode == KM_JIT) {
+    unsigned char* mp = mask.data_ptr<uint8_t>();
+    void* params[] = {&a, &mp};
+    TORCH_CHECK(hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(jit), plan.nwg, 1, 1, NTHR, 1, 1, 0,
+                                      c10::hip::getCurrentHIPStream().stream(), params, nullptr) == hipSuccess,
+                "pipe_mask: compiled kernel launch failed");
     return mask;
   }
-  choose_tile(a, 0, tile, 0);
-  if (a.kmode == 1) predecode_tile(a);
-  auto mask = torch::empty({n}, lit.options().dtype(torch::kUInt8));
-  if (n > 0) {
-    const long long per = a.tile ? (long long)a.tile : (long long)NTHR * ROWS * 4;
-    const int nwg = (int)std::max<long long>(1, std::min<long long>(a.tile ? 2048 : 4096, (n + per - 1) / per));
-    const int rc = nsdb_pipe_mask(&a, mask.data_ptr<uint8_t>(), nwg, c10::hip::getCurrentHIPStream().stream());
-    TORCH_CHECK(rc == 0, "pipe_mask launch failed: ", rc);
-  }
+  const int rc = nsdb_pipe_mask(&a, mask.data_ptr<uint8_t>(), plan.nwg, c10::hip::getCurrentHIPStream().stream());
+  TORCH_CHECK(rc == 0, "pipe_mask launch failed: ", rc);
   return mask;
+}
+
+// The plan pipe_agg (mask false) or pipe_mask (mask true: nins_a, key_reg, val_regs and agg_op are ignored, as
+// pipe_mask has none) would launch with for these arguments, and nothing else: the arguments are validated and the
+// form decided exactly as for a launch (column alignment decides it, so the column tensors are needed), but no
+// kernel runs and no device memory is read or allocated.
+pybind11::dict pipe_plan(torch::Tensor prog, int64_t nins_a, ColList cols, torch::Tensor lit, int64_t n, int64_t keep_reg,
+                         int64_t key_reg, std::vector<int64_t> val_regs, int64_t agg_op, int64_t max_wg, int64_t tile,
+                         std::vector<int64_t> kpool, int64_t jit, int64_t jit_nreg, int64_t jit_rows,
+                         c10::optional<torch::Tensor> jtab, c10::optional<torch::Tensor> jperm, int64_t bn,
+                         c10::optional<torch::Tensor> jbloom, bool mask) {
+  PipeArgs a;
+  const bool join = !mask && jtab.has_value() && jtab->defined();
+  if (mask) fill_args(a, prog, prog.size(0), cols, lit, n, keep_reg, -1, {}, 0, kpool);
+  else fill_args(a, prog, nins_a, cols, lit, n, keep_reg, key_reg, val_regs, agg_op, kpool, join ? bn : -1);
+  TORCH_CHECK(!join || jit != 0, "pipe_agg: a fused join needs its compiled kernel");
+  (void)jperm;
+  (void)jbloom;
+  const LaunchPlan p = plan_launch(a, mask, max_wg, tile, jit, jit_nreg, jit_rows);
+  pybind11::dict d;
+  d["kmode"] = p.kmode;
+  d["tile"] = p.tile;
+  d["lds_bytes"] = p.lds_bytes;
+  d["nreg"] = p.nreg;
+  d["rows"] = p.rows;
+  d["F"] = p.F;
+  d["nwg"] = p.nwg;
+  return d;
 }
 
 }  // namespace
@@ -534,6 +593,15 @@ void register_pipeline(pybind11::module& m) {
         pybind11::arg("jit") = 0, pybind11::arg("jit_nreg") = 0, pybind11::arg("jit_rows") = 0,
         pybind11::arg("jtab") = pybind11::none(), pybind11::arg("jperm") = pybind11::none(), pybind11::arg("bn") = -1,
         pybind11::arg("jbloom") = pybind11::none());
+  m.def("pipe_plan", &pipe_plan,
+        "the launch plan of pipe_agg (or, mask = True, pipe_mask) for these arguments, launching nothing: kmode (0 "
+        "register, 1 LDS-tile, 2 hybrid, 3 compiled), tile, lds_bytes, nreg, rows per thread, F, nwg",
+        pybind11::arg("prog"), pybind11::arg("nins_a"), pybind11::arg("cols"), pybind11::arg("lit"), pybind11::arg("n"),
+        pybind11::arg("keep_reg"), pybind11::arg("key_reg"), pybind11::arg("val_regs"), pybind11::arg("agg_op") = 0,
+        pybind11::arg("max_wg") = 0, pybind11::arg("tile") = -1, pybind11::arg("kpool") = std::vector<int64_t>(),
+        pybind11::arg("jit") = 0, pybind11::arg("jit_nreg") = 0, pybind11::arg("jit_rows") = 0,
+        pybind11::arg("jtab") = pybind11::none(), pybind11::arg("jperm") = pybind11::none(), pybind11::arg("bn") = -1,
+        pybind11::arg("jbloom") = pybind11::none(), pybind11::arg("mask") = false);
   m.def("pipe_emit", &pipe_emit,
         "fused stage, high-cardinality form: every kept (matched) row's emitted registers as dense int64 columns "
         "[ne, rows], and the host status (overflow, rows through segment A)",

@@ -292,12 +292,27 @@ __device__ __forceinline__ unsigned slot_hash(long long k) {
   return (unsigned)(z >> 40);
 }
 
+// min / max order doubles as the engine's group-by does (relops.hip ord_of: the IEEE totalOrder of the bit
+// patterns): -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN. So a NaN is a value like any other (a min drops a
+// positive NaN unless the group holds nothing else, a max returns it), -0.0 < +0.0, and the result never depends on
+// the order the rows arrive in. fmin / fmax would drop every NaN and leave the sign of a zero to that order.
+__device__ __forceinline__ u64 f64_ord(double v) {
+  const u64 b = f2u(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
 __device__ __forceinline__ double acc_op(double a, double b, int op) {
-  return op == 0 ? a + b : (op == 1 ? fmin(a, b) : fmax(a, b));
+  return op == 0 ? a + b : (op == 1 ? (f64_ord(b) < f64_ord(a) ? b : a) : (f64_ord(b) > f64_ord(a) ? b : a));
+}
+// the identity of the aggregation: 0 for a sum, the last / first double of that order for min / max
+__device__ __forceinline__ double agg_init(int op) {
+  return op == 0 ? 0.0 : u2f(op == 1 ? 0x7FFFFFFFFFFFFFFFull : 0xFFFFFFFFFFFFFFFFull);
 }
 
 // *p = op(*p, v) atomically (LDS or global: the pointer's address space is known after inlining). Sums use the
-// hardware f64 add atomic, min / max a 64-bit CAS loop.
+// hardware f64 add atomic, min / max a 64-bit CAS loop on the bit patterns: it leaves when the stored value already
+// is the result (bits compared, so a NaN or a zero of the other sign on either side cannot keep it spinning or skip
+// a store), or when its CAS lands; a failed CAS means another thread moved the value, which only ever moves one way
+// through a finite order.
 __device__ __forceinline__ void atomic_acc(double* p, double v, int op) {
   if (op == 0) {
     atomicAdd(p, v);
@@ -306,10 +321,9 @@ __device__ __forceinline__ void atomic_acc(double* p, double v, int op) {
   u64* q = reinterpret_cast<u64*>(p);
   u64 old = *q;
   while (true) {
-    const double cur = u2f(old);
-    const double nv = acc_op(cur, v, op);
-    if (nv == cur) return;
-    const u64 got = atomicCAS(q, old, f2u(nv));
+    const u64 nv = f2u(acc_op(u2f(old), v, op));
+    if (nv == old) return;
+    const u64 got = atomicCAS(q, old, nv);
     if (got == old) return;
     old = got;
   }
@@ -378,7 +392,7 @@ __device__ __forceinline__ void jit_agg_body(const PipeArgs& a) {
   // the aggregation op as a compile-time constant when the generated program fixes it (P::OP >= 0): a run-time op made
   // every accumulate compute the sum, the min and the max and select (1,303 v_max / v_min_f64 in TPC-H Q01's kernel)
   const int op = P::OP >= 0 ? P::OP : a.agg_op;
-  const double init = op == 0 ? 0.0 : (op == 1 ? __builtin_inf() : -__builtin_inf());
+  const double init = agg_init(op);
   for (int i = tid; i < CAP; i += NTHR) tk[i] = EMPTY;
   for (int i = tid; i < CAP * FMAX; i += NTHR) tv[i] = init;
   if (tid == 0) {
@@ -686,7 +700,7 @@ __device__ __forceinline__ void jit_join_agg_body(const PipeArgs& a) {
   __shared__ unsigned long long s_kept;
   const int tid = threadIdx.x;
   const int op = P::OP >= 0 ? P::OP : a.agg_op;     // compile-time when the program fixes it (see jit_agg_body)
-  const double init = op == 0 ? 0.0 : (op == 1 ? __builtin_inf() : -__builtin_inf());
+  const double init = agg_init(op);
   for (int i = tid; i < CAP; i += NTHR) tk[i] = EMPTY;
   for (int i = tid; i < CAP * FMAX; i += NTHR) tv[i] = init;
   if (tid == 0) {

@@ -1639,8 +1639,14 @@ def _merge(k: torch.Tensor, v: torch.Tensor, op: str):
     if op == "sum":
         out = torch.zeros(g, v.shape[1], dtype=torch.float64, device=v.device).index_add_(0, inv, v)
     else:
-        out = torch.zeros(g, v.shape[1], dtype=torch.float64, device=v.device).scatter_reduce_(
-            0, inv.unsqueeze(1).expand_as(v), v, "amin" if op == "min" else "amax", include_self=False)
+        # min / max in the IEEE totalOrder of the bit patterns, as the device group-by (relops.hip ord_of) and the
+        # fused kernels (pipeline_core.h acc_op) order doubles: -NaN < -inf < -0.0 < +0.0 < +inf < +NaN. As signed
+        # integers: a non-negative pattern is itself, a negative one has its low 63 bits flipped.
+        b = v.contiguous().view(torch.int64)
+        o = torch.where(b < 0, b ^ 0x7FFFFFFFFFFFFFFF, b)
+        o = torch.zeros(g, v.shape[1], dtype=torch.int64, device=v.device).scatter_reduce_(
+            0, inv.unsqueeze(1).expand_as(o), o, "amin" if op == "min" else "amax", include_self=False)
+        out = torch.where(o < 0, o ^ 0x7FFFFFFFFFFFFFFF, o).view(torch.float64)
     return uniq, out
 
 

@@ -448,7 +448,15 @@ def test_pipe_kernel_shapes_gpu():
     cols = PL._col_args(gprog, dev)
     lit = torch.zeros(1, dtype=torch.uint8, device=dev)
     pt = torch.tensor(ins, dtype=torch.int64)
+    # the kernel form each tile value really runs (pipe_plan: the launchers' own decision). This 8-register program's
+    # 2048-row tile needs 128 KiB of LDS per workgroup, three of which must share a CU: the binding answers that
+    # request with the register kernels, so 2048 here is one more register-kernel run (the 2048-row tile kernels are
+    # run by tests/test_pipeline_opcodes.py::test_tile2048_gpu on programs that fit them)
+    forms = {0: (0, 0), -1: (2, 1024), -2: (1, None), 512: (1, 512), 768: (1, 768), 1024: (1, 1024), 2048: (0, 0)}
     for tile in (0, -1, -2, 512, 768, 1024, 2048):
+        for plan in (h.pipe_plan(pt, 2, cols, lit, n, 5, 6, [4, 7], 0, 0, tile),
+                     h.pipe_plan(pt[:2], 2, cols, lit, n, 5, -1, [], 0, 0, tile, mask=True)):
+            assert plan["kmode"] == forms[tile][0] and forms[tile][1] in (None, plan["tile"]), (tile, plan)
         st, kept, k, v = _table_result(h.pipe_agg(pt, 2, cols, lit, n, 5, 6, [4, 7], 0, 0, tile), 2)
         assert st == 0 and kept == int(ref_mask.sum()), tile
         assert torch.equal(k, ref_k), tile
