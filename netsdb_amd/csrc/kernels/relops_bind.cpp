@@ -50,6 +50,10 @@ int nsdb_order_limit_max_k();
 long long nsdb_order_limit_state_bytes(const int* dt, int m, long long n);
 int nsdb_order_limit(const void* const* keys, const int* dt, const int* desc, int m, long long n, long long k,
                      void* state, unsigned* lists, unsigned* win, long long* out, hipStream_t st);
+int nsdb_order_by_tile();
+int nsdb_order_by_plan(const int* dt, int m, long long n, long long* fields);
+int nsdb_order_by(const void* const* keys, const int* dt, const int* desc, int m, long long n, long long limit,
+                  void* state, void* counts, void* words, void* ids, long long* out, hipStream_t st);
 }
 
 namespace {
@@ -549,6 +553,60 @@ torch::Tensor order_limit(std::vector<torch::Tensor> keys, std::vector<bool> des
         "order_limit");
   return out;
 }
+
+// The launch plan of order_by for these key dtype codes (0 int32, 1 float32, 2 int64, 3 float64) and n rows
+// (sort_plan.h); launches nothing. rc: 0, -1 bad key count, -2 bad dtype, -3 n outside [1, 2^31).
+pybind11::dict order_by_plan(std::vector<int64_t> dtypes, int64_t n) {
+  int dt[4] = {0, 0, 0, 0};
+  const int m = (int)dtypes.size();
+  for (int j = 0; j < m && j < 4; ++j) dt[j] = (int)dtypes[j];
+  long long f[12];
+  nsdb_order_by_plan(dt, m, n, f);
+  static const char* names[12] = {"rc", "word_bits", "tile", "tiles", "passes", "launches", "scan_step", "state_bytes",
+                                  "counts_bytes", "words_bytes", "ids_bytes", "scratch_bytes"};
+  pybind11::dict d;
+  for (int i = 0; i < 12; ++i) d[names[i]] = (int64_t)f[i];
+  return d;
+}
+
+// ORDER BY keys[0], keys[1], ... (sort.hip): the int64 row ids of all n rows in final order, or of the first `limit`
+// (limit < 0: all). Keys and order as order_limit. No host read: a linear chain of launches on the current stream, every
+// scratch buffer sized by the plan and taken from the caching allocator.
+torch::Tensor order_by(std::vector<torch::Tensor> keys, std::vector<bool> desc, int64_t limit) {
+  const int m = (int)keys.size();
+  TORCH_CHECK(m >= 1 && m <= 4, "order_by: 1 to 4 key columns");
+  TORCH_CHECK((int)desc.size() == m, "order_by: one direction per key");
+  const int64_t n = keys[0].numel();
+  const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+  int dt[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
+  for (int j = 0; j < m; ++j) {
+    auto& c = keys[j];
+    TORCH_CHECK(c.is_cuda() && c.dim() == 1 && c.numel() == n && c.device() == keys[0].device(),
+                "order_by: keys must be 1-D GPU columns of equal length on one device");
+    const auto t = c.scalar_type();
+    dt[j] = t == torch::kInt32 ? 0 : t == torch::kFloat32 ? 1 : t == torch::kInt64 ? 2 : t == torch::kFloat64 ? 3 : -1;
+    TORCH_CHECK(dt[j] >= 0, "order_by: keys must be int32, int64, float32 or float64");
+    c = c.contiguous();
+    ptr[j] = c.data_ptr();
+    ds[j] = desc[j] ? 1 : 0;
+  }
+  auto i64 = keys[0].options().dtype(torch::kInt64);
+  if (n == 0 || limit == 0) return torch::empty({0}, i64);
+  TORCH_CHECK(n < (int64_t(1) << 31), "order_by: at most 2^31 - 1 rows");
+  const int64_t lim = limit < 0 ? n : std::min<int64_t>(limit, n);
+  long long f[12];
+  TORCH_CHECK(nsdb_order_by_plan(dt, m, n, f) == 0, "order_by: bad key set (plan code ", f[0], ")");
+  const int64_t state_b = f[7], counts_b = f[8], words_b = f[9], ids_b = f[10];
+  auto state = torch::zeros({(state_b + 7) / 8}, i64);
+  auto counts = torch::empty({(counts_b + 7) / 8}, i64);
+  auto words = torch::empty({(words_b + 7) / 8}, i64);
+  auto ids = torch::empty({(ids_b + 7) / 8}, i64);
+  auto out = torch::empty({lim}, i64);
+  rc_ok(nsdb_order_by(ptr, dt, ds, m, n, lim, state.data_ptr(), counts.data_ptr(), words.data_ptr(), ids.data_ptr(),
+                      LL(out.data_ptr<int64_t>()), stream()),
+        "order_by");
+  return out;
+}
 }  // namespace
 
 std::vector<torch::Tensor> hash_aggregate_impl(torch::Tensor keys, c10::optional<torch::Tensor> vals,
@@ -589,6 +647,13 @@ void register_relops(pybind11::module& m) {
   m.def("order_limit", &order_limit, "ORDER BY keys (desc[j]: key j descending; ties by row id) LIMIT k: int64 row ids "
         "in final order, no host read", pybind11::arg("keys"), pybind11::arg("desc"), pybind11::arg("k"));
   m.attr("ORDER_LIMIT_MAX_K") = nsdb_order_limit_max_k();
+  m.def("order_by", &order_by, "ORDER BY keys (desc[j]: key j descending; ties by row id): int64 row ids of all rows, "
+        "or of the first `limit` (< 0: all), in final order, no host read", pybind11::arg("keys"), pybind11::arg("desc"),
+        pybind11::arg("limit") = -1);
+  m.def("order_by_plan", &order_by_plan, "launch plan of order_by for dtype codes (0 i32, 1 f32, 2 i64, 3 f64) and n "
+        "rows: rc, word_bits, tile, tiles, passes, launches, scan_step and the scratch bytes by buffer",
+        pybind11::arg("dtypes"), pybind11::arg("n"));
+  m.attr("ORDER_BY_TILE") = nsdb_order_by_tile();
   m.def("mix64", &mix64, "key hash mix64((x ^ y) + GOLD) per row, one pass", pybind11::arg("x"),
         pybind11::arg("y") = pybind11::none());
 }

@@ -997,6 +997,13 @@ class QueryEngine:
         agg = agg_parts[0] if len(agg_parts) == 1 else column_concat(agg_parts)
         return reps, agg
 
+    def _topk_ids(self, sc, k):
+        """Row ids of the k best scores, best first, ties lowest row first: K.order_limit up to its largest k, the
+        full device ORDER BY with a limit (K.order_by, sort.hip) above it."""
+        if k > K.ORDER_LIMIT_MAX_K:
+            return K.order_by([sc], True, stats=self.pipeline_stats, limit=k)
+        return K.order_limit([sc], k, descending=True, stats=self.pipeline_stats)
+
     def _topk(self, comp, batches, kcol, vcol, out_ts, out_col, state):
         """TopKComp: per-rank top k by score on the device (K.order_limit, topk.hip, over the device score column;
         objects gathered with a device take), then the ranks' candidates meet through one packed all-gather and the
@@ -1013,14 +1020,13 @@ class QueryEngine:
             ob = column_concat(objs)
             dev = scores[0].device
             sc = torch.cat([s.to(dev) for s in scores])
-            top = K.order_limit([sc], comp.k, descending=True, stats=self.pipeline_stats)
+            top = self._topk_ids(sc, comp.k)
             local = RecordBatch({"o": column_take(ob, top), "s": sc.index_select(0, top)}, int(top.numel()))
         if self.ctx.distributed:
             got = [g for g in self.ctx.broadcast_batch_all(local) if g is not None and g.n]
             local = RecordBatch.concat(got) if got else None
             if local is not None:
-                local = local.take(K.order_limit([local.columns["s"]], comp.k, descending=True,
-                                                 stats=self.pipeline_stats))
+                local = local.take(self._topk_ids(local.columns["s"], comp.k))
             if self.ctx.rank != 0:
                 local = None
         if local is None or local.n == 0:

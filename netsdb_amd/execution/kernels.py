@@ -114,6 +114,97 @@ def order_limit(keys, k: int, descending=False, stats: Optional[dict] = None) ->
     return order[:k]
 
 
+# Rows from which the device radix sort (sort.hip) takes an ORDER BY of GPU columns by default, by key count; None: that
+# key count stays on torch's argsort chain unless path="device" asks. Measured, not chosen: the smallest size of the
+# 2^12 .. 2^24 sweep from which the device arm's median stays below the torch arm's minimum
+# (profiles/order_by/README.md). Three keys (f64 desc, i32, i64): from 262,144 rows (0.376 against 0.387 ms; 16 M rows:
+# 3.54 against 4.57). One key: an int32 key of 2,500 values crosses at 262,144 rows too (two live passes), but one
+# float64 key never does (16 M rows: 1.60 against 1.35 ms: eight live passes of count + scan + scatter each), so one
+# key stays on torch. Two and four keys have not been measured and stay on torch.
+_ORDER_BY_MIN_ROWS = {1: None, 2: None, 3: 1 << 18, 4: None}
+ORDER_BY_TILE = 4096         # rows one scatter workgroup ranks (sort_plan.h kSortTile; the extension's ORDER_BY_TILE)
+_ORDER_DT_CODE = {torch.int32: 0, torch.float32: 1, torch.int64: 2, torch.float64: 3}
+
+
+def _order_native(dt: torch.dtype) -> torch.dtype:
+    """The dtype order_limit / order_by read a key column of dtype ``dt`` in."""
+    if dt in _ORDER_NATIVE:
+        return dt
+    return torch.float64 if dt.is_floating_point else torch.int64
+
+
+def order_by_plan(dtypes, n: int, device_is_gpu: bool, path: Optional[str] = None) -> dict:
+    """What ``order_by`` does with key columns of these torch dtypes and n rows, without launching anything:
+    ``{"path": "torch" | "order_limit" | "radix", ...}``; for ``radix`` also the host plan of sort.hip (sort_plan.h:
+    word_bits, tile, tiles, passes, launches, scan_step, and state / counts / words / ids / scratch bytes). ``path``
+    as in ``order_by``."""
+    dts = [_order_native(d) for d in dtypes]
+    if not 1 <= len(dts) <= 4:
+        raise ValueError("order_by: 1 to 4 key columns")
+    if path not in (None, "device", "torch"):
+        raise ValueError("order_by: path is None, 'device' or 'torch'")
+    n = int(n)
+    if path == "device" and (not device_is_gpu or n >= (1 << 31)):
+        raise ValueError("order_by: path='device' needs GPU columns of fewer than 2^31 rows")
+    if not device_is_gpu or path == "torch" or n == 0 or n >= (1 << 31):
+        return {"path": "torch"}
+    if n <= ORDER_LIMIT_MAX_K:
+        return {"path": "order_limit"}
+    lo = _ORDER_BY_MIN_ROWS[len(dts)]
+    if path != "device" and (lo is None or n < lo):
+        return {"path": "torch"}
+    plan = dict(_ext.hip().order_by_plan([_ORDER_DT_CODE[d] for d in dts], n))
+    if plan.pop("rc") != 0:
+        raise ValueError("order_by: no plan for this key set")
+    plan["path"] = "radix"
+    return plan
+
+
+def order_by(keys, descending=False, stats: Optional[dict] = None, limit: Optional[int] = None,
+             path: Optional[str] = None) -> torch.Tensor:
+    """ORDER BY keys[0], keys[1], ...: the int64 row ids of all n rows in final order, or of the first
+    ``min(limit, n)`` when ``limit`` is given.
+
+    Keys, directions and the total order are ``order_limit``'s, word for word (NaN above +inf, -0.0 equal to +0.0,
+    rows equal on every key by ascending row id): the result is the stable-argsort chain that ``order_limit``
+    documents, without ``[:k]``. CPU columns take that chain. GPU columns of at most ORDER_LIMIT_MAX_K rows go to
+    ``order_limit(keys, n)`` under its own dispatch; longer ones (below 2^31 rows) take sort.hip — a stable LSD radix
+    sort over the order words, no host read, graph-capturable, counted in ``stats["device_order_by"]`` — from the
+    measured size ``_ORDER_BY_MIN_ROWS`` of their key count on, and the chain below it. ``path="device"`` or
+    ``path="torch"`` forces an arm (tests and benchmarks); ``"device"`` on CPU columns raises. ``order_by_plan``
+    answers which arm a call takes."""
+    cols = [keys] if isinstance(keys, torch.Tensor) else list(keys)
+    if not 1 <= len(cols) <= 4:
+        raise ValueError("order_by: 1 to 4 key columns")
+    desc = [bool(descending)] * len(cols) if isinstance(descending, (bool, int)) else [bool(d) for d in descending]
+    if len(desc) != len(cols):
+        raise ValueError("order_by: one direction, or one per key")
+    n = int(cols[0].numel())
+    for i, c in enumerate(cols):
+        if c.dim() != 1 or int(c.numel()) != n:
+            raise ValueError("order_by: keys must be one-dimensional columns of equal length")
+        if c.dtype not in _ORDER_NATIVE:
+            cols[i] = c.double() if c.is_floating_point() else c.long()
+    plan = order_by_plan([c.dtype for c in cols], n, all(c.is_cuda for c in cols), path)
+    if n == 0 or (limit is not None and int(limit) <= 0):
+        return torch.empty(0, dtype=torch.int64, device=cols[0].device)
+    k = n if limit is None else min(int(limit), n)
+    if plan["path"] == "radix":
+        out = _ext.hip().order_by(cols, desc, k)
+        if stats is not None:
+            stats["device_order_by"] = stats.get("device_order_by", 0) + 1
+        return out
+    if plan["path"] == "order_limit":
+        return order_limit(cols, k, desc, stats=stats)
+    order = None
+    for c, d in zip(reversed(cols), reversed(desc)):
+        if order is None:
+            order = torch.argsort(c, descending=d, stable=True)
+        else:
+            order = order[torch.argsort(c[order], descending=d, stable=True)]
+    return order[:k]
+
+
 def _obj_key(v) -> int:
     if isinstance(v, RecordView):
         v = v.as_tuple()

@@ -489,6 +489,13 @@ class RecordBatch:
 
         return self.take(K.order_limit([self.columns[c] for c in cols], k, descending))
 
+    def order_by(self, cols: Sequence[str], descending=False, limit: Optional[int] = None) -> "RecordBatch":
+        """ORDER BY the named (numeric tensor) columns: every row in final order, or the first ``min(limit, n)``
+        (execution.kernels.order_by: ``descending`` one bool or one per column, ties by row id)."""
+        from ..execution import kernels as K
+
+        return self.take(K.order_by([self.columns[c] for c in cols], descending, limit=limit))
+
     def slice(self, s: int, e: int) -> "RecordBatch":
         cols = {k: column_slice(c, s, e) for k, c in self.columns.items()}
         return RecordBatch(cols, max(0, min(e, self.n) - s), self.type)

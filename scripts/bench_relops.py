@@ -7,9 +7,11 @@
   * partition permutation of 16 M rows over 8 destinations: partition_perm vs argsort(stable) + bincount;
   * ORDER BY ... LIMIT k (K.order_limit, topk.hip) at --rows: one float64 key descending, k = 10 / 100 / 2048, vs
     torch.topk + a sort of the k values; three keys (float64 descending, int32, int64), k = 10, vs the chain of three
-    stable argsorts.
+    stable argsorts;
+  * ORDER BY without LIMIT (K.order_by) at --rows, path="device" (sort.hip) vs path="torch" (the stable-argsort chain):
+    one int32 key in a date-like range of 2,500 values, one float64 key, three keys (float64 descending, int32, int64).
 
-    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json] [--sections order_limit]
+    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json] [--sections order_limit|order_by]
 """
 import argparse
 import json
@@ -86,17 +88,48 @@ def bench_order_limit(a, out):
     print(json.dumps({"order_limit": "3key_k10", **t}), flush=True)
 
 
+def bench_order_by(a, out):
+    """K.order_by: the device radix sort against the argsort chain, both arms alternating in the same rounds."""
+    dev = "cuda:0"
+    n = a.rows
+    g = torch.Generator(device=dev).manual_seed(2)
+    out["order_by"] = {}
+    x = torch.rand(n, device=dev, dtype=torch.float64, generator=g)
+    od = torch.randint(0, 2500, (n,), device=dev, generator=g, dtype=torch.int32)
+    ok = torch.randint(0, 1 << 40, (n,), device=dev, generator=g, dtype=torch.int64)
+    rev = torch.floor(x * (n / 16)) / (n / 16)         # about 16 rows share each value: keys 1 and 2 decide inside
+    shapes = (("1key_i32_dates", "i32 in [0, 2500)", [od], [False]),
+              ("1key_f64", "f64", [x], [False]),
+              ("3key", "f64 desc, i32, i64", [rev, od, ok], [True, False, False]))
+    for name, what, keys, desc in shapes:
+        def device_arm():
+            return K.order_by(keys, desc, path="device")
+
+        def torch_arm():
+            return K.order_by(keys, desc, path="torch")
+
+        assert torch.equal(device_arm(), torch_arm()), "order_by: the device arm differs from the argsort chain"
+        t = run({"order_by_device": device_arm, "order_by_torch": torch_arm}, a.rounds)
+        t["keys"], t["rows"] = what, n
+        t["plan"] = K.order_by_plan([c.dtype for c in keys], n, True, "device")["path"]
+        out["order_by"][name] = t
+        print(json.dumps({"order_by": name, **t}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=16_000_000)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--sections", default="all", help="all, or order_limit alone (the other sections run together)")
+    ap.add_argument("--sections", default="all", help="all, or order_limit / order_by alone (the other sections run together)")
     a = ap.parse_args()
     out = {"rows": a.rows}
-    if a.sections != "order_limit":
+    if a.sections not in ("order_limit", "order_by"):
         bench_tables(a, out)
-    bench_order_limit(a, out)
+    if a.sections != "order_by":
+        bench_order_limit(a, out)
+    if a.sections != "order_limit":
+        bench_order_by(a, out)
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
         with open(a.json, "w") as f:
