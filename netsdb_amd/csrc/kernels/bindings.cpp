@@ -73,6 +73,12 @@ int nsdb_str_eq_pairs(const void* a, const int64_t* sta, const int64_t* ena, con
                       hipStream_t st);
 int nsdb_str_gather(const void* src, const int64_t* starts, const int64_t* ends, const int64_t* idx,
                     const int64_t* out_off, int64_t m, void* dst, hipStream_t st);
+int nsdb_str_order_words(const void* bytes, const int64_t* starts, const int64_t* ends, int64_t nrows,
+                         const int64_t* ids, int64_t m, int64_t first_chunk, int count, int64_t* out_words,
+                         int32_t* out_len, hipStream_t st);
+int nsdb_str_cmp_pairs(const void* a, const int64_t* sta, const int64_t* ena, const int64_t* ia, const void* b,
+                       const int64_t* stb, const int64_t* enb, const int64_t* ib, int64_t m, int8_t* out,
+                       hipStream_t st);
 }
 
 void register_relops(pybind11::module& m);
@@ -763,6 +769,69 @@ torch::Tensor str_eq_pairs(torch::Tensor a, torch::Tensor sta, torch::Tensor ena
   return out.view(torch::kBool);
 }
 
+// out[i] = -1 / 0 / +1 for a[ia[i]] against b[ib[i]] in unsigned-byte lexicographic order (a proper prefix first);
+// ia / ib may be None (identity). The three-way sibling of str_eq_pairs.
+torch::Tensor str_cmp_pairs(torch::Tensor a, torch::Tensor sta, torch::Tensor ena, c10::optional<torch::Tensor> ia,
+                            torch::Tensor b, torch::Tensor stb, torch::Tensor enb, c10::optional<torch::Tensor> ib,
+                            int64_t m) {
+  check_strings(a, sta, ena);
+  check_strings(b, stb, enb);
+  TORCH_CHECK(m >= 0, "m must be >= 0");
+  const int64_t* pa = nullptr;
+  const int64_t* pb = nullptr;
+  if (ia.has_value() && ia->defined()) {
+    check_cuda(*ia, "ia");
+    TORCH_CHECK(ia->scalar_type() == torch::kInt64 && ia->is_contiguous() && ia->numel() == m, "ia i64 [m]");
+    pa = ia->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(sta.numel() >= m, "a has fewer than m rows");
+  }
+  if (ib.has_value() && ib->defined()) {
+    check_cuda(*ib, "ib");
+    TORCH_CHECK(ib->scalar_type() == torch::kInt64 && ib->is_contiguous() && ib->numel() == m, "ib i64 [m]");
+    pb = ib->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(stb.numel() >= m, "b has fewer than m rows");
+  }
+  auto out = torch::empty({m}, a.options().dtype(torch::kInt8));
+  check_rc(nsdb_str_cmp_pairs(a.data_ptr(), sta.data_ptr<int64_t>(), ena.data_ptr<int64_t>(), pa, b.data_ptr(),
+                              stb.data_ptr<int64_t>(), enb.data_ptr<int64_t>(), pb, m, out.data_ptr<int8_t>(),
+                              cur_stream()),
+           "str_cmp_pairs");
+  return out;
+}
+
+// Order words of a string key (strings.hip str_order_words_kernel): for output i < m, row ids[i] (ids None: row i, m =
+// the row count), the sortable int64 words of chunks [first, first + count), count <= 4, as the rows of one [count, m]
+// tensor, and the int32 row lengths when with_len. Returns (words, lengths or an undefined tensor). An id outside the
+// column is written as the empty row; no chunk past a row's end is loaded.
+std::vector<torch::Tensor> str_order_words(torch::Tensor bytes, torch::Tensor st, torch::Tensor en, int64_t payload_end,
+                                           c10::optional<torch::Tensor> ids, int64_t first, int64_t count,
+                                           bool with_len) {
+  check_strings(bytes, st, en);
+  TORCH_CHECK(payload_end + 16 <= bytes.numel(), "string payload must be followed by >= 16 pad bytes");
+  TORCH_CHECK(first >= 0 && first <= (int64_t(1) << 40), "str_order_words: first chunk out of range");
+  TORCH_CHECK(count >= 0 && count <= 4, "str_order_words: 0 to 4 chunks a call");
+  TORCH_CHECK(count > 0 || with_len, "str_order_words: nothing to write");
+  const int64_t nrows = st.numel();
+  const int64_t* ip = nullptr;
+  int64_t m = nrows;
+  if (ids.has_value() && ids->defined()) {
+    check_cuda(*ids, "ids");
+    TORCH_CHECK(ids->scalar_type() == torch::kInt64 && ids->is_contiguous() && ids->dim() == 1, "ids i64 1-D");
+    ip = ids->data_ptr<int64_t>();
+    m = ids->numel();
+  }
+  auto words = torch::empty({count, m}, st.options());
+  torch::Tensor lens;
+  if (with_len) lens = torch::empty({m}, st.options().dtype(torch::kInt32));
+  check_rc(nsdb_str_order_words(bytes.data_ptr(), st.data_ptr<int64_t>(), en.data_ptr<int64_t>(), nrows, ip, m, first,
+                                (int)count, count ? words.data_ptr<int64_t>() : nullptr,
+                                with_len ? lens.data_ptr<int32_t>() : nullptr, cur_stream()),
+           "str_order_words");
+  return {words, lens};
+}
+
 // SUBSTRING of every row: out_off [n+1] (device prefix sums of the clamped lengths), cap = an upper bound of the
 // output bytes known on the host (n * length): no device read to size the buffer.
 torch::Tensor str_slice(torch::Tensor bytes, torch::Tensor st, torch::Tensor en, int64_t start, torch::Tensor out_off,
@@ -931,6 +1000,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("str_eq_pairs", &str_eq_pairs, "byte-exact equality of string row pairs a[ia[i]] == b[ib[i]]",
         py::arg("a"), py::arg("sta"), py::arg("ena"), py::arg("ia"), py::arg("b"), py::arg("stb"), py::arg("enb"),
         py::arg("ib"), py::arg("m"));
+  m.def("str_cmp_pairs", &str_cmp_pairs, "three-way byte order of string row pairs a[ia[i]] against b[ib[i]] (int8)",
+        py::arg("a"), py::arg("sta"), py::arg("ena"), py::arg("ia"), py::arg("b"), py::arg("stb"), py::arg("enb"),
+        py::arg("ib"), py::arg("m"));
+  m.def("str_order_words", &str_order_words,
+        "sortable int64 words of 8-byte chunks [first, first + count) of the rows ids (None: all), and the lengths",
+        py::arg("bytes"), py::arg("starts"), py::arg("ends"), py::arg("payload_end"), py::arg("ids"), py::arg("first"),
+        py::arg("count"), py::arg("with_len"));
   m.def("str_gather", &str_gather, "pack rows of a device string column into a new padded byte buffer",
         py::arg("bytes"), py::arg("starts"), py::arg("ends"), py::arg("idx"), py::arg("out_off"), py::arg("out_bytes"));
 }

@@ -6,7 +6,9 @@
 //  * nsdb_str_hash   — 64-bit hash per string (group-by / join keys, IN-lists),
 //  * nsdb_str_like   — SQL LIKE with '%' and single-byte '_' (=, prefix, suffix, contains are the
 //                      1-segment special cases), pattern in the kernarg segment (scalar loads),
-//  * nsdb_str_gather — take(): copy selected strings into a new packed buffer.
+//  * nsdb_str_gather — take(): copy selected strings into a new packed buffer,
+//  * nsdb_str_order_words / nsdb_str_cmp_pairs — ORDER BY on a string key: sortable 8-byte chunk words for the
+//                      device sorts, and the three-way row compare that turns a sorted order into dense ranks.
 //
 // One lane per string: TPC-H / Reddit strings are 1-120 bytes, so 64 neighbouring strings of a wave
 // are a few contiguous KB that the L1/L2 serve from a handful of lines. Bytes are read as aligned
@@ -323,6 +325,74 @@ __global__ __launch_bounds__(256) void str_eq_pairs_kernel(const uint32_t* __res
   out[i] = eq ? 1 : 0;
 }
 
+// ORDER BY on a string key: the order is the unsigned bytes' lexicographic order, a proper prefix first (embedded NUL
+// bytes are bytes like any other). Chunk t of a row is its bytes [8t, 8t + 8) big-endian with zero bytes past the row's
+// end, sign bit flipped so that int64 order is the chunks' unsigned order. Rows compare as the word sequence
+// (chunk 0, chunk 1, ..., length): zero padding makes the shorter string smaller at the first chunk where the padded
+// bytes differ, and when every padded chunk is equal the longer string is the shorter one plus NUL bytes, which the
+// length word decides. The words are plain int64 / int32 key columns for sort.hip / topk.hip (StringColumn.order_perm).
+//
+// Output i < m describes row ids[i] (ids null: row i) and writes out_words[t' * m + i] for chunks first + t',
+// t' < count <= 4, and the row length to out_len when given. A chunk at or past the row's end is the zero chunk WITHOUT
+// a load: 8 * first can lie any distance past the row, and the buffer is padded by 16 bytes only. An id outside
+// [0, nrows) reads nothing and is written as the empty row (zero chunks, length 0).
+__global__ __launch_bounds__(256) void str_order_words_kernel(const uint32_t* __restrict__ w,
+                                                             const int64_t* __restrict__ st,
+                                                             const int64_t* __restrict__ en, int64_t nrows,
+                                                             const int64_t* __restrict__ ids, int64_t m, int64_t first,
+                                                             int count, int64_t* __restrict__ out_words,
+                                                             int32_t* __restrict__ out_len) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int64_t r = ids ? ids[i] : i;
+  int64_t s = 0, len = 0;
+  if (r >= 0 && r < nrows) {
+    s = st[r];
+    len = en[r] - s;
+    if (len < 0) len = 0;
+  }
+  for (int t = 0; t < count; ++t) {
+    const int64_t p = 8 * (first + t);
+    uint64_t be = 0;
+    if (p < len) {
+      uint64_t c = load8(w, s + p);
+      const int64_t rem = len - p;
+      if (rem < 8) c &= (1ull << (8 * rem)) - 1ull;
+      be = __builtin_bswap64(c);
+    }
+    out_words[(int64_t)t * m + i] = (int64_t)(be ^ 0x8000000000000000ull);
+  }
+  if (out_len) out_len[i] = (int32_t)len;
+}
+
+// Three-way sibling of str_eq_pairs_kernel: -1 / 0 / +1 for a[ia[i]] against b[ib[i]] in the order above, 8 bytes at a
+// time over the common length (byte-swap, mask the tail, unsigned compare); the lengths decide last.
+__global__ __launch_bounds__(256) void str_cmp_pairs_kernel(const uint32_t* __restrict__ wa, const int64_t* __restrict__ sta,
+                                                            const int64_t* __restrict__ ena, const int64_t* __restrict__ ia,
+                                                            const uint32_t* __restrict__ wb, const int64_t* __restrict__ stb,
+                                                            const int64_t* __restrict__ enb, const int64_t* __restrict__ ib,
+                                                            int64_t m, int8_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const int64_t ra = ia ? ia[i] : i, rb = ib ? ib[i] : i;
+  const int64_t sa = sta[ra], la = ena[ra] - sa;
+  const int64_t sb = stb[rb], lb = enb[rb] - sb;
+  const int64_t mn = la < lb ? la : lb;
+  int c = 0;
+  for (int64_t p = 0; c == 0 && p < mn; p += 8) {
+    uint64_t x = load8(wa, sa + p), y = load8(wb, sb + p);
+    const int64_t rem = mn - p;
+    if (rem < 8) {
+      const uint64_t mask = (1ull << (8 * rem)) - 1ull;
+      x &= mask;
+      y &= mask;
+    }
+    if (x != y) c = __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
+  }
+  if (c == 0) c = la < lb ? -1 : (la > lb ? 1 : 0);
+  out[i] = (int8_t)c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -418,6 +488,30 @@ int nsdb_str_eq_pairs(const void* a, const int64_t* sta, const int64_t* ena, con
                       hipStream_t st) {
   if (m <= 0) return 0;
   hipLaunchKernelGGL(str_eq_pairs_kernel, dim3(grid_for(m)), dim3(256), 0, st, (const uint32_t*)a, sta, ena, ia,
+                     (const uint32_t*)b, stb, enb, ib, m, out);
+  return (int)hipGetLastError();
+}
+
+// Order words of rows ids[0..m) (ids null: rows 0..m, m <= nrows) for chunks [first_chunk, first_chunk + count),
+// count <= 4, to out_words [count * m] (chunk-major), and the row lengths to out_len [m] when given. count == 0 with
+// out_len is the length-only call.
+int nsdb_str_order_words(const void* bytes, const int64_t* starts, const int64_t* ends, int64_t nrows,
+                         const int64_t* ids, int64_t m, int64_t first_chunk, int count, int64_t* out_words,
+                         int32_t* out_len, hipStream_t st) {
+  if (count < 0 || count > 4 || first_chunk < 0 || first_chunk > (int64_t(1) << 40)) return -2;
+  if (nrows < 0 || (!ids && m > nrows)) return -2;
+  if (m <= 0) return 0;
+  if ((count == 0 && !out_len) || (count > 0 && !out_words)) return -2;
+  hipLaunchKernelGGL(str_order_words_kernel, dim3(grid_for(m)), dim3(256), 0, st, (const uint32_t*)bytes, starts, ends,
+                     nrows, ids, m, first_chunk, count, out_words, out_len);
+  return (int)hipGetLastError();
+}
+
+int nsdb_str_cmp_pairs(const void* a, const int64_t* sta, const int64_t* ena, const int64_t* ia, const void* b,
+                       const int64_t* stb, const int64_t* enb, const int64_t* ib, int64_t m, int8_t* out,
+                       hipStream_t st) {
+  if (m <= 0) return 0;
+  hipLaunchKernelGGL(str_cmp_pairs_kernel, dim3(grid_for(m)), dim3(256), 0, st, (const uint32_t*)a, sta, ena, ia,
                      (const uint32_t*)b, stb, enb, ib, m, out);
   return (int)hipGetLastError();
 }

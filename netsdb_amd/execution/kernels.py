@@ -21,7 +21,7 @@ import xxhash
 
 from .. import _ext
 from ..objects.record import RecordBatch, RecordView
-from ..objects.strings import StringColumn, hash_str, is_string_list
+from ..objects.strings import StringColumn, as_strings, hash_str, is_string_list
 
 _M1 = -0x40A7B892E31B1A47   # 0xBF58476D1CE4E5B9 as signed int64
 _M2 = -0x6B2FB644ECCEEE15   # 0x94D049BB133111EB as signed int64
@@ -73,18 +73,33 @@ _ORDER_LARGE_K_MIN_ROWS = 1 << 16
 _ORDER_NATIVE = (torch.int32, torch.int64, torch.float32, torch.float64)
 
 
+def _order_key_columns(keys, path: Optional[str], stats: Optional[dict]) -> list:
+    """The key list of order_limit / order_by with every string key (a StringColumn, or a host list[str] through
+    as_strings on the other keys' device) replaced by its int32 dense ranks (StringColumn.order_codes: code order is
+    the strings' byte order, equal strings tie), so everything after this sees numeric columns only."""
+    single = isinstance(keys, (torch.Tensor, StringColumn)) or is_string_list(keys)
+    cols = [keys] if single else list(keys)
+    dev = next((c.device for c in cols if isinstance(c, (torch.Tensor, StringColumn))), None)
+    for i, c in enumerate(cols):
+        if isinstance(c, StringColumn) or is_string_list(c):
+            cols[i] = as_strings(c, dev).order_codes(path=path, stats=stats)
+    return cols
+
+
 def order_limit(keys, k: int, descending=False, stats: Optional[dict] = None) -> torch.Tensor:
     """ORDER BY keys[0], keys[1], ... LIMIT k: the int64 row ids of the first ``min(k, n)`` rows, in final order.
 
     ``keys``: 1 to 4 one-dimensional columns of equal length n (int32 / int64 / float32 / float64 as they are, other
-    integer and bool columns through ``.long()``, other float columns through ``.double()``); ``descending``: one bool
+    integer and bool columns through ``.long()``, other float columns through ``.double()``; a string key — a
+    StringColumn, or a host ``list[str]`` — through its int32 dense ranks ``StringColumn.order_codes``: unsigned-byte
+    lexicographic order, a proper prefix first, equal strings tie); ``descending``: one bool
     or one per key. The order is total: lexicographic over the keys; inside a float key NaN orders above +inf and
     -0.0 equals +0.0 (torch's sort order); rows equal on every key by ascending row id. That is the first
     ``min(k, n)`` entries of the stable-argsort chain below (the CPU path, the path of k above ORDER_LIMIT_MAX_K or of
     many rows kept out of few, and the reference). On the GPU: topk.hip (radix select + one small sort; no host read,
     graph-capturable), counted in ``stats["device_order_limit"]`` when ``stats`` (e.g. an engine's pipeline_stats) is
     given."""
-    cols = [keys] if isinstance(keys, torch.Tensor) else list(keys)
+    cols = _order_key_columns(keys, None, stats)
     if not 1 <= len(cols) <= 4:
         raise ValueError("order_limit: 1 to 4 key columns")
     desc = [bool(descending)] * len(cols) if isinstance(descending, (bool, int)) else [bool(d) for d in descending]
@@ -137,7 +152,8 @@ def order_by_plan(dtypes, n: int, device_is_gpu: bool, path: Optional[str] = Non
     """What ``order_by`` does with key columns of these torch dtypes and n rows, without launching anything:
     ``{"path": "torch" | "order_limit" | "radix", ...}``; for ``radix`` also the host plan of sort.hip (sort_plan.h:
     word_bits, tile, tiles, passes, launches, scan_step, and state / counts / words / ids / scratch bytes). ``path``
-    as in ``order_by``."""
+    as in ``order_by``. A string key plans as ``torch.int32`` (its dense ranks, which ``order_by`` sorts in its
+    place; computing them is ``string_order_plan``'s chain, not part of this plan)."""
     dts = [_order_native(d) for d in dtypes]
     if not 1 <= len(dts) <= 4:
         raise ValueError("order_by: 1 to 4 key columns")
@@ -172,8 +188,10 @@ def order_by(keys, descending=False, stats: Optional[dict] = None, limit: Option
     sort over the order words, no host read, graph-capturable, counted in ``stats["device_order_by"]`` — from the
     measured size ``_ORDER_BY_MIN_ROWS`` of their key count on, and the chain below it. ``path="device"`` or
     ``path="torch"`` forces an arm (tests and benchmarks); ``"device"`` on CPU columns raises. ``order_by_plan``
-    answers which arm a call takes."""
-    cols = [keys] if isinstance(keys, torch.Tensor) else list(keys)
+    answers which arm a call takes. A string key is replaced by ``StringColumn.order_codes`` first; ``path`` and
+    ``stats`` go there too, so ``stats["device_string_order"]`` counts each string key whose ranks were computed
+    on a GPU and ``device_order_by`` / ``device_order_limit`` also count the sorts of that chain's groups."""
+    cols = _order_key_columns(keys, path, stats)
     if not 1 <= len(cols) <= 4:
         raise ValueError("order_by: 1 to 4 key columns")
     desc = [bool(descending)] * len(cols) if isinstance(descending, (bool, int)) else [bool(d) for d in descending]

@@ -483,15 +483,15 @@ class RecordBatch:
         return RecordBatch(cols, n, self.type)
 
     def order_limit(self, cols: Sequence[str], k: int, descending=False) -> "RecordBatch":
-        """ORDER BY the named (numeric tensor) columns LIMIT k: the first ``min(k, n)`` rows in final order
-        (execution.kernels.order_limit: ``descending`` one bool or one per column, ties by row id)."""
+        """ORDER BY the named columns (numeric tensors, string columns) LIMIT k: the first ``min(k, n)`` rows in final
+        order (execution.kernels.order_limit: ``descending`` one bool or one per column, ties by row id)."""
         from ..execution import kernels as K
 
         return self.take(K.order_limit([self.columns[c] for c in cols], k, descending))
 
     def order_by(self, cols: Sequence[str], descending=False, limit: Optional[int] = None) -> "RecordBatch":
-        """ORDER BY the named (numeric tensor) columns: every row in final order, or the first ``min(limit, n)``
-        (execution.kernels.order_by: ``descending`` one bool or one per column, ties by row id)."""
+        """ORDER BY the named columns (numeric tensors, string columns): every row in final order, or the first
+        ``min(limit, n)`` (execution.kernels.order_by: ``descending`` one bool or one per column, ties by row id)."""
         from ..execution import kernels as K
 
         return self.take(K.order_by([self.columns[c] for c in cols], descending, limit=limit))

@@ -140,6 +140,47 @@ def _like_regex(pat, st, ln, a0, a1) -> "re.Pattern[bytes]":
     return re.compile((rb"\A" if a0 else b"") + (body if a0 else b".*" + body) + (rb"\Z" if a1 else b""), re.S)
 
 
+def string_order_plan(max_len: int, n: int) -> dict:
+    """How :meth:`StringColumn.order_perm` orders n rows of at most ``max_len`` bytes, without launching anything.
+
+    A row orders as the word sequence ``[chunk 0, ..., chunk R-1, length]``, R = ``chunks`` = ceil(max_len / 8)
+    (strings.hip str_order_words_kernel: big-endian 8-byte chunks, zero bytes past the row's end, then the length).
+    ``groups`` cuts that list into runs of at most 4 words (the key limit of ``order_by``) from the back, LEAST
+    SIGNIFICANT FIRST: one ``(first_chunk, count, with_len)`` per ``order_words`` + ``order_by`` call of the LSD chain.
+    ``words`` = R + 1, ``rows`` = n."""
+    max_len, n = int(max_len), int(n)
+    if max_len < 0 or n < 0:
+        raise ValueError("string_order_plan: max_len and n must be >= 0")
+    chunks = (max_len + 7) // 8
+    groups, hi, with_len = [], chunks, True
+    while True:
+        count = min(hi, 3 if with_len else 4)
+        groups.append((hi - count, count, with_len))
+        hi -= count
+        with_len = False
+        if hi == 0:
+            break
+    return {"chunks": chunks, "words": chunks + 1, "groups": groups, "rows": n}
+
+
+_SIGN64 = np.uint64(1 << 63)
+
+
+def _order_words_np(buf: np.ndarray, st: np.ndarray, ln: np.ndarray, first: int, count: int) -> np.ndarray:
+    """Host twin of str_order_words_kernel: [count, m] int64 words of the rows (st, ln)."""
+    m = st.size
+    out = np.empty((count, m), dtype=np.int64)
+    j = np.arange(8, dtype=np.int64)
+    for t in range(count):
+        p = 8 * (first + t)
+        live = (p + j)[None, :] < ln[:, None]
+        byts = buf[np.where(live, st[:, None] + p + j[None, :], 0)].astype(np.uint64)
+        byts[~live] = 0
+        word = (byts << (np.uint64(8) * (7 - j).astype(np.uint64))[None, :]).sum(1, dtype=np.uint64)
+        out[t] = (word ^ _SIGN64).view(np.int64)
+    return out
+
+
 class StringColumn:
     """n strings over one uint8 buffer ``data`` [>= payload + 16] (4-byte multiple): row i is
     ``data[starts[i]:ends[i]]``. A PACKED column (built from a list, gathered, read from a page) also keeps
@@ -148,7 +189,7 @@ class StringColumn:
     rows costs two device gathers and no device->host read. Kernels take (starts, ends) and so run on either
     form; :attr:`offsets` (serialisation, shuffles) packs a view in place on first use."""
 
-    __slots__ = ("data", "starts", "ends", "_off", "payload", "buf_rows", "_maxlen", "_codes")
+    __slots__ = ("data", "starts", "ends", "_off", "payload", "buf_rows", "_maxlen", "_codes", "_order_codes")
 
     def __init__(self, data: torch.Tensor, offsets: torch.Tensor, payload: int, buf_rows: Optional[int] = None,
                  maxlen: Optional[int] = None):
@@ -159,6 +200,7 @@ class StringColumn:
             maxlen = int(np.diff(offsets.numpy()).max())       # host offsets: free to bound here
         self._maxlen = maxlen     # upper bound of the row lengths (None: not known yet, see max_len)
         self._codes = None        # (L, short codes) once computed: the column's fixed-width encoding, kept
+        self._order_codes = None  # dense int32 ranks once computed (order_codes), kept like the short codes
 
     @staticmethod
     def view(data: torch.Tensor, starts: torch.Tensor, ends: torch.Tensor, payload: int,
@@ -167,6 +209,7 @@ class StringColumn:
         c.data, c.starts, c.ends, c._off, c.payload, c.buf_rows = data, starts, ends, None, int(payload), buf_rows
         c._maxlen = maxlen
         c._codes = None
+        c._order_codes = None
         return c
 
     # ------------------------------------------------------------------ construction
@@ -502,6 +545,107 @@ class StringColumn:
             eq[idx] = ok.astype(bool)
         return torch.from_numpy(eq)
 
+    # ------------------------------------------------------------------ ORDER BY on a string key
+    # The order: the unsigned bytes of the UTF-8 encoding, lexicographically, a proper prefix first (code-point order
+    # for valid UTF-8; embedded NUL bytes are bytes like any other); equal strings tie. In Python:
+    # sorted(range(n), key=lambda i: (s[i].encode(), i)).
+
+    def order_words(self, first: int, count: int, ids: Optional[torch.Tensor] = None, with_len: bool = False):
+        """The sortable words of chunks ``[first, first + count)``, ``0 <= count <= 4``, as a tuple of int64 columns,
+        plus the int32 row lengths when ``with_len``. Entry i describes row ``ids[i]`` (``ids`` None: row i). Chunk t
+        is the row's bytes ``[8t, 8t + 8)`` big-endian, zero bytes past the row's end, sign bit flipped so that int64
+        order is the unsigned order; an id outside the column gives the empty row's words and length 0. One
+        str_order_words launch on the GPU (no host read), numpy on the CPU."""
+        first, count = int(first), int(count)
+        if first < 0 or not 0 <= count <= 4 or (count == 0 and not with_len):
+            raise ValueError("order_words: first >= 0, 0 to 4 chunks, and something to write")
+        dev = self.device
+        if ids is not None:
+            ids = ids.to(dev).long().contiguous()
+        if dev.type == "cuda":
+            words, lens = _ext.hip().str_order_words(self.data, self.starts.contiguous(), self.ends.contiguous(),
+                                                     self.payload, ids, first, count, bool(with_len))
+            return tuple(words.unbind(0)) + ((lens,) if with_len else ())
+        st, ln = self.starts.numpy(), (self.ends - self.starts).numpy()
+        if ids is not None:
+            ii = ids.numpy()
+            ok = (ii >= 0) & (ii < st.size)
+            st, ln = np.append(st, 0)[np.where(ok, ii, st.size)], np.append(ln, 0)[np.where(ok, ii, ln.size)]
+        ln = np.maximum(ln, 0)
+        words = _order_words_np(self.data.numpy(), st, ln, first, count)
+        out = tuple(torch.from_numpy(words[t]) for t in range(count))
+        return out + ((torch.from_numpy(ln.astype(np.int32)),) if with_len else ())
+
+    def cmp_rows(self, ia: Optional[torch.Tensor], other: "StringColumn", ib: Optional[torch.Tensor]) -> torch.Tensor:
+        """Three-way ``self[ia[i]]`` against ``other[ib[i]]`` for every i (ia / ib None: the identity) in the order
+        above, as int8 -1 / 0 / +1: the sibling of :meth:`eq_rows` (str_cmp_pairs on the GPU)."""
+        m = len(self) if ia is None else ia.numel()
+        dev = self.device
+        other = other.to(dev)
+        if m == 0:
+            return torch.zeros(0, dtype=torch.int8, device=dev)
+        # resolve the indices into row bounds with index_select (bounds-checked by torch, no host read)
+        sa, ea = (self.starts, self.ends) if ia is None else (self.starts.index_select(0, ia.to(dev).long()),
+                                                              self.ends.index_select(0, ia.to(dev).long()))
+        sb, eb = (other.starts, other.ends) if ib is None else (other.starts.index_select(0, ib.to(dev).long()),
+                                                                other.ends.index_select(0, ib.to(dev).long()))
+        if sb.numel() < m:
+            raise IndexError("cmp_rows: other has fewer rows than compared")
+        if dev.type == "cuda":
+            return _ext.hip().str_cmp_pairs(self.data, sa.contiguous(), ea.contiguous(), None, other.data,
+                                            sb.contiguous(), eb.contiguous(), None, m)
+        ra, rb = self.data.numpy().tobytes(), other.data.numpy().tobytes()
+        out = np.fromiter(((ra[s:e] > rb[t:u]) - (ra[s:e] < rb[t:u]) for s, e, t, u in
+                           zip(sa.tolist()[:m], ea.tolist()[:m], sb.tolist()[:m], eb.tolist()[:m])),
+                          dtype=np.int8, count=m)
+        return torch.from_numpy(out)
+
+    def order_perm(self, path: Optional[str] = None, stats: Optional[dict] = None) -> torch.Tensor:
+        """The int64 row ids of all rows in ascending order, equal strings by ascending row id.
+
+        A least-significant-first chain over the groups of :func:`string_order_plan`: each group's words
+        (:meth:`order_words`, read through the permutation so far) are sorted by ``execution.kernels.order_by``, which
+        is stable, so each later, more significant group refines the order of the earlier ones. ``path`` goes to
+        ``order_by`` unchanged: with None every group takes ``order_by``'s own measured dispatch for its key count
+        and size. ``stats`` goes there too (``device_order_by`` / ``device_order_limit`` count the groups that took a
+        device sort), and ``stats["device_string_order"]`` counts this call once when the column is on a GPU.
+
+        The plan needs the bound :meth:`max_len`, one cached device->host read when it is not known yet, so the chain
+        is graph-capturable only for a column whose bound is already known (built from a list, a ``take`` / ``substr``
+        of such a column); everything after the bound stays on the device."""
+        from ..execution.kernels import order_by
+
+        n = len(self)
+        perm = None
+        for first, count, with_len in string_order_plan(self.max_len(), n)["groups"]:
+            words = self.order_words(first, count, ids=perm, with_len=with_len)
+            q = order_by(list(words), False, stats=stats, path=path)
+            perm = q if perm is None else perm.index_select(0, q)
+        if stats is not None and self.device.type == "cuda":
+            stats["device_string_order"] = stats.get("device_string_order", 0) + 1
+        return perm
+
+    def order_codes(self, path: Optional[str] = None, stats: Optional[dict] = None) -> torch.Tensor:
+        """int32 dense rank per row: the number of distinct smaller strings of the column. Equal strings have equal
+        codes and code order is string order, so a string key sorts (and compares) as one int32 column.
+
+        From :meth:`order_perm` (``path`` / ``stats`` go there): rows that differ from their predecessor in sorted
+        order (:meth:`cmp_rows`) start a new rank; a cumulative sum gives the rank at every sorted position and one
+        scatter takes the ranks back to the rows. Computed once and kept with the column like the short codes (same
+        lifetime; a ``take`` / ``substr`` / ``concat`` result has its own rows and never inherits them). Callers must
+        not modify the returned tensor in place."""
+        if self._order_codes is not None and self._order_codes.device == self.device:
+            return self._order_codes
+        n, dev = len(self), self.device
+        codes = torch.zeros(n, dtype=torch.int32, device=dev)
+        if n:
+            p = self.order_perm(path=path, stats=stats)
+            rank = torch.zeros(n, dtype=torch.int32, device=dev)
+            rank[1:] = torch.cumsum(self.cmp_rows(p[1:], self, p[:-1]) != 0, 0)
+            codes.index_copy_(0, p, rank)
+        self._order_codes = codes
+        return codes
+
     def _match(self, compiled, negate=False) -> torch.Tensor:
         pat, st, ln, a0, a1 = compiled
         if self.device.type == "cuda":
@@ -560,11 +704,22 @@ class StringColumn:
             return torch.tensor([s in allowed for s in self.tolist()], dtype=torch.bool, device=self.device)
         return cand & self.eq_rows(None, ref, order.index_select(0, pos))
 
-    def dict_encode(self):
+    def dict_encode(self, sorted: bool = False):
         """(codes int64 [n], dictionary list[str]): device unique over the hashes; only the distinct
-        strings cross to the host."""
+        strings cross to the host. ``sorted=True``: the dictionary is in key order and the codes are
+        :meth:`order_codes` (code order = string order); the first row of each run of equal codes is read."""
         from ..execution.kernels import group_ids   # exact (hash + byte re-check) grouping
 
+        if sorted:
+            codes = self.order_codes().long()
+            n = len(self)
+            if n == 0:
+                return codes, []
+            # the first row (smallest id) of every distinct string: scatter-min of the row ids over the codes
+            ndist = int(codes.max()) + 1
+            firsts = torch.full((ndist,), n, dtype=torch.int64, device=self.device)
+            firsts.scatter_reduce_(0, codes, torch.arange(n, device=self.device), "amin")
+            return codes, self.take(firsts).tolist()
         inv, reps, _ = group_ids(self)
         return inv, reps.tolist()
 
@@ -577,4 +732,4 @@ def as_strings(c, device=None) -> StringColumn:
     return c if isinstance(c, StringColumn) else StringColumn.from_list(c, device)
 
 
-__all__ = ["StringColumn", "hash_str", "use_device_strings", "is_string_list", "as_strings"]
+__all__ = ["StringColumn", "hash_str", "use_device_strings", "is_string_list", "as_strings", "string_order_plan"]

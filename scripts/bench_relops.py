@@ -9,9 +9,13 @@
     torch.topk + a sort of the k values; three keys (float64 descending, int32, int64), k = 10, vs the chain of three
     stable argsorts;
   * ORDER BY without LIMIT (K.order_by) at --rows, path="device" (sort.hip) vs path="torch" (the stable-argsort chain):
-    one int32 key in a date-like range of 2,500 values, one float64 key, three keys (float64 descending, int32, int64).
+    one int32 key in a date-like range of 2,500 values, one float64 key, three keys (float64 descending, int32, int64);
+  * ORDER BY one string key (StringColumn.order_perm and K.order_by on the column) at --rows, every sort of the chain on
+    path="device" vs path="torch": 25 distinct nation names, unique 'Supplier#%09d' names, random lowercase strings
+    of 8 to 40 bytes; and once at 1 M rows against the host's sorted(col.tolist()).
 
-    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json] [--sections order_limit|order_by]
+    python scripts/bench_relops.py [--rows 16000000] [--rounds 5] [--json out.json]
+                                   [--sections order_limit|order_by|order_by_str]
 """
 import argparse
 import json
@@ -116,20 +120,93 @@ def bench_order_by(a, out):
         print(json.dumps({"order_by": name, **t}), flush=True)
 
 
+NATIONS = ["ALGERIA", "ARGENTINA", "BRAZIL", "CANADA", "EGYPT", "ETHIOPIA", "FRANCE", "GERMANY", "INDIA", "INDONESIA",
+           "IRAN", "IRAQ", "JAPAN", "JORDAN", "KENYA", "MOROCCO", "MOZAMBIQUE", "PERU", "CHINA", "ROMANIA",
+           "SAUDI ARABIA", "VIETNAM", "RUSSIA", "UNITED KINGDOM", "UNITED STATES OF AMERICA"]
+
+
+def _string_shapes(n, dev, g):
+    """The three string key columns of the order_by_str section, built on the device (no n-row host list)."""
+    from netsdb_amd.objects.strings import StringColumn
+
+    def packed(data, off, payload, maxlen):
+        buf = torch.zeros(((payload + 16 + 3) // 4) * 4, dtype=torch.uint8, device=dev)
+        buf[:payload] = data
+        return StringColumn(buf, off, payload, maxlen=maxlen)
+
+    nation = StringColumn.from_list(NATIONS, dev).take(torch.randint(0, len(NATIONS), (n,), device=dev, generator=g))
+    ids = torch.randperm(n, device=dev, generator=g) + 1
+    digits = (ids.unsqueeze(1) // (10 ** torch.arange(8, -1, -1, device=dev)).unsqueeze(0)) % 10 + ord("0")
+    prefix = torch.tensor(list(b"Supplier#"), dtype=torch.uint8, device=dev).expand(n, 9)
+    supp = packed(torch.cat([prefix, digits.to(torch.uint8)], 1).flatten(), torch.arange(n + 1, device=dev) * 18,
+                  18 * n, 18)
+    lens = torch.randint(8, 41, (n,), device=dev, generator=g)
+    off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=off[1:])
+    total = int(off[-1])
+    text = packed(torch.randint(ord("a"), ord("z") + 1, (total,), device=dev, generator=g, dtype=torch.uint8), off,
+                  total, 40)
+    return (("nation_25_distinct", "25 distinct names, L = 24", nation),
+            ("supplier_unique", "'Supplier#%09d' unique, L = 18", supp),
+            ("lowercase_8_40", "random lowercase, 8..40 bytes", text))
+
+
+def bench_order_by_str(a, out):
+    """ORDER BY one string key (StringColumn.order_perm: order words + the LSD chain over K.order_by; K.order_by on
+    the column: that chain, the dense ranks, and the sort of the ranks): path="device" against path="torch" for every
+    sort of the chain, both arms alternating in the same rounds; then once at 1 M rows against the host
+    sorted(col.tolist()) that a caller had to do before. ``col[:]`` is a fresh column over the same buffers each call,
+    so no call finds kept ranks."""
+    from netsdb_amd.objects.strings import string_order_plan
+
+    dev = "cuda:0"
+    out["order_by_str"] = {}
+    for n, host in ((a.rows, False), (1_000_000, True)):
+        g = torch.Generator(device=dev).manual_seed(3)
+        for name, what, col in _string_shapes(n, dev, g):
+            fns = {f"{fn}_{path}": (lambda fn=fn, path=path: (
+                col[:].order_perm(path=path) if fn == "order_perm" else K.order_by([col[:]], path=path)))
+                for fn in ("order_perm", "order_by") for path in ("device", "torch")}
+            ref = fns["order_perm_device"]()
+            for k, f in fns.items():
+                assert torch.equal(f(), ref), f"order_by_str: {k} differs"
+            t = run(fns, a.rounds)
+            t["keys"], t["rows"] = what, n
+            t["groups"] = string_order_plan(col.max_len(), n)["groups"]
+            if host:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                strs = col.tolist()
+                t1 = time.perf_counter()
+                ordered = sorted(strs)
+                t2 = time.perf_counter()
+                assert ordered == [strs[i] for i in ref.cpu().tolist()], "order_by_str: differs from the host sort"
+                t["host_tolist_ms"], t["host_sorted_ms"] = round((t1 - t0) * 1e3, 1), round((t2 - t1) * 1e3, 1)
+                t["default"] = run({"order_perm_default": lambda: col[:].order_perm()}, a.rounds)["order_perm_default"]
+            key = f"{name}_{n}"
+            out["order_by_str"][key] = t
+            print(json.dumps({"order_by_str": key, **t}), flush=True)
+            del col, fns, ref
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=16_000_000)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--sections", default="all", help="all, or order_limit / order_by alone (the other sections run together)")
+    ap.add_argument("--sections", default="all",
+                    help="all, or order_limit / order_by / order_by_str alone (the other sections run together)")
     a = ap.parse_args()
     out = {"rows": a.rows}
-    if a.sections not in ("order_limit", "order_by"):
+    alone = ("order_limit", "order_by", "order_by_str")
+    if a.sections not in alone:
         bench_tables(a, out)
-    if a.sections != "order_by":
+    if a.sections not in alone or a.sections == "order_limit":
         bench_order_limit(a, out)
-    if a.sections != "order_limit":
+    if a.sections not in alone or a.sections == "order_by":
         bench_order_by(a, out)
+    if a.sections not in alone or a.sections == "order_by_str":
+        bench_order_by_str(a, out)
     if a.json:
         os.makedirs(os.path.dirname(a.json) or ".", exist_ok=True)
         with open(a.json, "w") as f:
