@@ -37,7 +37,7 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
 // Compile-time activation (kernels templated on ACT: no per-element switch in unrolled epilogues).
 template <int ACT>
 __device__ __forceinline__ float act_t(float v) {
-  if constexpr (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
+  if constexpr (ACT == ACT_RELU) return v < 0.f ? 0.f : v;       // NaN stays NaN (as torch.relu)
   else if constexpr (ACT == ACT_SIGMOID) return 1.f / (1.f + __expf(-v));
   else if constexpr (ACT == ACT_EXP) return __expf(v);
   else if constexpr (ACT == ACT_TANH) return tanhf(v);
@@ -46,7 +46,7 @@ __device__ __forceinline__ float act_t(float v) {
 
 __device__ __forceinline__ float apply_act(float v, int act) {
   switch (act) {
-    case ACT_RELU: return v > 0.f ? v : 0.f;
+    case ACT_RELU: return v < 0.f ? 0.f : v;                       // NaN stays NaN (as torch.relu)
     case ACT_SIGMOID: return 1.f / (1.f + __expf(-v));
     case ACT_EXP: return __expf(v);
     case ACT_TANH: return tanhf(v);
@@ -59,7 +59,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // 128-element unrolled epilogue stays small enough to be fully unrolled (no acc spill to scratch).
 __device__ __forceinline__ float apply_act_compact(float v, int act) {
   if (act == ACT_NONE) return v;
-  if (act == ACT_RELU) return fmaxf(v, 0.f);
+  if (act == ACT_RELU) return v < 0.f ? 0.f : v;                   // not fmaxf: NaN stays NaN
   const float a = act == ACT_EXP ? 1.f : (act == ACT_SIGMOID ? -1.f : -2.f);
   const float t = __expf(a * v);
   if (act == ACT_EXP) return t;

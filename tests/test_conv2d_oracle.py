@@ -493,6 +493,35 @@ def test_conv2d_nonfinite_pixels(dev, plan, geom, opts, yout, nan_at, inf_at):
               f"8-tap window {int(window.sum())}")
 
 
+@pytest.mark.parametrize("plan,geom,opts,yout,nan_at,inf_at", NONFINITE_CASES,
+                         ids=[f"{c[0]}-{_sid(c[1])}" for c in NONFINITE_CASES])
+@pytest.mark.parametrize("dev", DEVS)
+def test_conv2d_relu_of_nan(dev, plan, geom, opts, yout, nan_at, inf_at):
+    """relu keeps NaN, as torch.relu and the CPU path do (``v > 0 ? v : 0`` gave 0): with one NaN pixel and relu,
+    every output of the pixel's receptive set is NaN, and everything outside the row kernels' 8-tap window is the
+    exact relu of the finite oracle (igemm and the CPU path: everything outside the receptive set)."""
+    (N, C, H, W, OC, KH, KW), s, p, d = geom
+    X0, W4, bias, _ = _exact(geom)
+    X = X0.clone()
+    X[nan_at] = float("nan")
+    ref = _oracle(X, W4, bias, s, p, d)
+    ref = torch.where(ref < 0, torch.zeros_like(ref), ref)               # relu that keeps NaN
+    OH, OW = ref.shape[2:]
+    n, _, h, w = nan_at
+    rows = slice(max(h + p - KH + 1, 0), min(h + p, OH - 1) + 1)
+    field = torch.zeros_like(ref, dtype=torch.bool)
+    window = torch.zeros_like(ref, dtype=torch.bool)
+    field[n, :, rows, max(w + p - KW + 1, 0): min(w + p, OW - 1) + 1] = True
+    window[n, :, rows, max(w + p - 7, 0): min(w + p, OW - 1) + 1] = True
+    assert torch.equal(ref.isnan(), field) and (ref[~field] == 0).any() and (ref[~field] > 0).any()
+    y = _conv(dev, geom, X, _flat(W4), bias, "relu", yout, True, opts, plan)
+    got = y.detach().cpu().double()
+    assert got[field].isnan().all(), (
+        f"{plan}: relu turned NaN into a number, first at {(field & ~got.isnan()).nonzero()[0].tolist()}")
+    exact = ~field if plan == "igemm" or dev == "cpu" else ~window
+    assert torch.equal(got[exact], ref.to(y.dtype).double()[exact]), f"{plan}: outputs away from the NaN are not exact"
+
+
 # ------------------------------------------------------------------------------------------- the offset sentinel
 
 @pytest.mark.parametrize("dev", DEVS)

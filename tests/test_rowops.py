@@ -316,6 +316,22 @@ def test_bias_act(dev, R, N, act, mode, xin, yout):
     _run_bias_act(dev, X, bias, mode, act, yout)
 
 
+@pytest.mark.parametrize("yout", ["f32", "bf16"])
+@pytest.mark.parametrize("mode", list(BIAS_MODES))
+@pytest.mark.parametrize("dev", DEVS)
+def test_bias_act_relu_of_nan(dev, mode, yout):
+    """relu keeps NaN (as torch.relu and the CPU path do), sends -Inf to 0 and keeps +Inf; ``v > 0 ? v : 0`` and
+    ``fmaxf(v, 0)`` both turn NaN into 0. ``_check`` requires the oracle's NaN pattern and its +-Inf exactly."""
+    R, N = 5, 9
+    g = _gen(95)
+    X = torch.randn(R, N, generator=g) * 3
+    X[0, 0], X[1, 3], X[2, 5], X[4, 8] = float("nan"), float("-inf"), float("inf"), float("nan")
+    bias = None if mode == "nobias" else torch.randn(R if mode == "row" else N, generator=g)
+    ref = _bias_act_oracle(X, bias, mode, "relu")
+    assert int(ref.isnan().sum()) == 2 and float(ref[1, 3]) == 0.0 and float(ref[2, 5]) == float("inf")
+    _run_bias_act(dev, X, bias, mode, "relu", yout)
+
+
 @pytest.mark.parametrize("act", ["none", "tanh"])
 @pytest.mark.parametrize("mode", ["row", "col"])
 @pytest.mark.parametrize("dev", DEVS)
