@@ -1847,6 +1847,10 @@ __global__ __launch_bounds__(256) void run_write_kernel(const u64* __restrict__ 
 
 // group g = rows [heads[g], heads[g + 1]) (the last ends at n): its key, row count and F reduced values (vals read in
 // place: element (row, f) at vals[row * rs + f * cs]); op 0 sum, 1 min, 2 max — in row order, as a sequential fold
+// with the hash paths' semantics (this is one path of the device group-by: the same rows must answer alike whether
+// they arrive in runs or not): a sum starts from the op's identity, so a run of only -0.0 sums to +0.0 and an int64
+// sum wraps modulo 2^64; min / max of doubles compare the ord_of images, i.e. by IEEE totalOrder of the bits
+// (-NaN < -inf < -0.0 < +0.0 < +inf < +NaN, a NaN is a value), wherever in its run a value sits.
 template <typename VT>
 __global__ __launch_bounds__(256) void run_reduce_kernel(const u64* __restrict__ k, const VT* __restrict__ vals,
                                                          i64 rs, i64 cs, int F, int op, i64 n,
@@ -1862,12 +1866,31 @@ __global__ __launch_bounds__(256) void run_reduce_kernel(const u64* __restrict__
     ocnt[g] = hi - lo;
     for (int f = 0; f < F; ++f) {
       const VT* p = vals + f * cs;
-      VT acc = p[lo * rs];
-      for (i64 r = lo + 1; r < hi; ++r) {
-        const VT x = p[r * rs];
-        acc = op == 0 ? acc + x : (op == 1 ? (x < acc ? x : acc) : (x > acc ? x : acc));
+      if (op == 0) {
+        if constexpr (__is_same(VT, double)) {
+          double acc = 0.0;
+          for (i64 r = lo; r < hi; ++r) acc += p[r * rs];
+          oagg[g * F + f] = acc;
+        } else {
+          u64 acc = 0;
+          for (i64 r = lo; r < hi; ++r) acc += (u64)p[r * rs];
+          oagg[g * F + f] = (VT)acc;
+        }
+      } else if constexpr (__is_same(VT, double)) {
+        u64 acc = ord_of(p[lo * rs]);
+        for (i64 r = lo + 1; r < hi; ++r) {
+          const u64 x = ord_of(p[r * rs]);
+          acc = op == 1 ? (x < acc ? x : acc) : (x > acc ? x : acc);
+        }
+        oagg[g * F + f] = ord_to_f64(acc);
+      } else {
+        VT acc = p[lo * rs];
+        for (i64 r = lo + 1; r < hi; ++r) {
+          const VT x = p[r * rs];
+          acc = op == 1 ? (x < acc ? x : acc) : (x > acc ? x : acc);
+        }
+        oagg[g * F + f] = acc;
       }
-      oagg[g * F + f] = acc;
     }
   }
 }

@@ -649,7 +649,8 @@ def group_reduce(keys, values, op: str = "sum"):
     else:
         agg = sel(aggs)
         if op == "mean":
-            agg = agg / cnt.unsqueeze(1).to(agg.dtype)
+            # in float64 for integer sums too (int64 / int64 would divide in the default float32)
+            agg = agg.double() / cnt.unsqueeze(1).double()
         out_dtype = values.dtype if (is_float or op != "mean") else torch.float64
         agg = agg.to(out_dtype).reshape((g,) + tuple(values.shape[1:]))
     if packed is not None and packed[1] is not None:
