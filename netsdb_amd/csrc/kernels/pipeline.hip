@@ -29,6 +29,10 @@
 //    the stage then runs the unfused path (more groups than this kernel is for). status[1] counts the kept rows.
 #include "common.h"
 #include "pipeline_core.h"
+#include "relops_plan.h"
+
+static_assert(nsdb_pipe::JREGION == nsdb::kJRegion && nsdb_pipe::JWHOLE == nsdb::kJWholeWrap,
+              "the fused probes (pipeline_core.h) and the join build (relops_plan.h) must walk the same probe order");
 
 namespace nsdb_pipe {
 

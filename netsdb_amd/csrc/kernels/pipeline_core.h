@@ -537,8 +537,9 @@ __device__ __forceinline__ u64 fin64(u64 x) {
 
 // build rows matching probe key k: cnt (0 = none) and the payload (the row when cnt == 1, else the run start)
 // Join tables of more than JWHOLE slots probe linearly INSIDE aligned regions of JREGION slots (wrapping at the
-// region's end, not the table's): relops.hip builds them region by region in LDS (kJRegion / kJWholeWrap there: the
-// values must be equal). Smaller tables: plain linear probing over the whole table.
+// region's end, not the table's): relops.hip builds them region by region in LDS. Smaller tables: plain linear
+// probing over the whole table. This header is a runtime-compiled program's only one, so it keeps its own copy of
+// relops_plan.h's kJRegion / kJWholeWrap; pipeline.hip asserts that the two agree.
 constexpr unsigned long long JREGION = 4096, JWHOLE = 1ull << 22;
 __device__ __forceinline__ unsigned long long jnext(unsigned long long s, unsigned long long mask) {
   const unsigned long long rm = mask < JWHOLE ? mask : JREGION - 1;

@@ -32,8 +32,13 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstddef>
+
+#include "relops_plan.h"
 
 namespace nsdb_rel {
+
+using namespace nsdb;   // the constants, geometry and buffer layouts the host decides: relops_plan.h
 
 typedef unsigned long long u64;
 typedef long long i64;
@@ -123,6 +128,15 @@ struct AggMeta {
   i64 lowp;           // key partitions of the MID path (low == 2)
   i64 pad[5];
 };
+static_assert(sizeof(AggMeta) / 8 == kMetaStructWords && offsetof(AggMeta, est) / 8 == kMetaEst &&
+                  offsetof(AggMeta, low) / 8 == kMetaLow && offsetof(AggMeta, ng_low) / 8 == kMetaNgLow &&
+                  offsetof(AggMeta, ng_part) / 8 == kMetaNgPart && offsetof(AggMeta, fail_low) / 8 == kMetaFailLow &&
+                  offsetof(AggMeta, fail_part) / 8 == kMetaFailPart &&
+                  offsetof(AggMeta, sentinel_low) / 8 == kMetaSentinelLow &&
+                  offsetof(AggMeta, sentinel_part) / 8 == kMetaSentinelPart &&
+                  offsetof(AggMeta, occ_low) / 8 == kMetaOccLow && offsetof(AggMeta, occ_part) / 8 == kMetaOccPart &&
+                  offsetof(AggMeta, lowp) / 8 == kMetaLowP,
+              "AggMeta and relops_plan.h's word indices");
 
 struct GTable {                     // open-addressing global table: cap slots + one slot (cap) for the kEmpty key
   u64* key;                         // [cap + 1], preset kEmpty
@@ -138,7 +152,7 @@ struct AggOut {
   i64* reps;        // [n] dense group keys
   u64* aggs;        // [n * F]
   i64* cnt;         // [n]
-  i64* slot_of_gid; // [n] (unused region of the output buffer: kept so the bindings' offsets stay put)
+  i64* slot_of_gid; // [n] written by nothing (relops_plan.h agg_out)
   i64* first;       // [n] smallest row index of each group (its representative row)
   i64* inv;         // [n] or null
 };
@@ -273,11 +287,6 @@ __device__ __forceinline__ void row_into_global(GTable g, u64 k, const VT* v, in
 // One workgroup hashes 4096 evenly spaced rows into an LDS table with per-key counts and writes the Chao1
 // estimate of the distinct keys, d + f1^2 / (2 f2) (f1 / f2: keys seen once / twice in the sample; exact d when
 // every row was sampled), clamped to [d, n]. The PART path sizes its sub-partitions from it.
-constexpr int kSample = 4096;
-// MID path: at most this many key partitions. Every workgroup of a row group reads all of its rows' keys through its
-// own CU, so the per-CU load stream grows with P: measured (profiles/r5_relops) 16 M rows, 10 k keys at P = 5 took
-// 0.65 ms against the PART path's 0.47, so MID stops at P = 3 (~6 k groups).
-constexpr int kMidPMax = 3;
 
 // The sampled rows' keys into sbuf[4096]: the random reads spread over 64 workgroups (one CU's outstanding-miss
 // budget made a single-workgroup sample latency-bound).
@@ -941,14 +950,9 @@ __global__ __launch_bounds__(256) void agg_fix_inv_kernel(i64* __restrict__ inv,
 }
 
 // ---------------------------------------------------------------- hash join
-// Tables of more than kJWholeWrap slots probe linearly inside aligned regions of kJRegion slots (a chain wraps at its
-// region's end) and are built region by region in LDS (join_region_build_kernel); smaller ones (builds up to ~1 M
-// rows, whose table fits the MALL) probe the whole table with plain linear probing and take the global-atomic insert
-// (no region can fill: no host check). Every probe (join_probe_kernel here, pipeline_core.h join_find /
-// join_find_rows, whose JREGION / JWHOLE must equal kJRegion / kJWholeWrap) walks the same order.
-constexpr int kJRegionBits = 12;
-constexpr u64 kJRegion = 1ull << kJRegionBits;
-constexpr u64 kJWholeWrap = 1ull << 22;   // tables of at most this many slots: chains wrap at the table's end
+// Tables of more than kJWholeWrap slots probe linearly inside aligned regions of kJRegion slots (relops_plan.h) and
+// are built region by region in LDS (join_region_build_kernel); smaller ones take the global-atomic insert (no region
+// can fill: no host check).
 __device__ __forceinline__ u64 jregion_mask(u64 mask) { return mask < kJWholeWrap ? mask : kJRegion - 1; }
 __device__ __forceinline__ u64 jnext(u64 s, u64 mask) {
   const u64 rm = jregion_mask(mask);
@@ -1226,7 +1230,7 @@ __global__ __launch_bounds__(kJPartThreads) void jpart_scatter_kernel(const u64*
 // The coarse scatter of a two-level partition (<= kJStageBins bins), staged through LDS: each 4096-row tile is
 // counting-sorted by bin in LDS, then written out bin run by bin run (consecutive threads, consecutive addresses of
 // one run: ~16 rows = 128 B of keys per run at 257 bins) instead of every row to a line of its own.
-constexpr int kJStageBins = 1024, kJTileRows = 4096;
+constexpr int kJTileRows = 4096;
 __global__ __launch_bounds__(kJPartThreads) void jpart_scatter_staged_kernel(
     const u64* __restrict__ keys, i64 n, i64 rpw, u64 mask, unsigned P, int sh, const unsigned* __restrict__ hist,
     const i64* __restrict__ bbase, u64* __restrict__ ikey, unsigned* __restrict__ irow) {
@@ -1506,7 +1510,6 @@ __global__ __launch_bounds__(256) void join_bloom_kernel(const JSlot* __restrict
   if (bits) __hip_atomic_fetch_or(bloom + w, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-constexpr int kJTile = 4096;   // probe rows per workgroup tile (256 threads x 16)
 
 
 // probe: matches (cnt) and payload per probe row, and the match total of each 4096-row tile. The first-slot
@@ -1708,7 +1711,7 @@ __global__ __launch_bounds__(256) void mix64_kernel(const u64* __restrict__ x, c
 // ---------------------------------------------------------------- stable stream compaction (mask -> row ids)
 // The row ids of the nonzero bytes of a 0/1 byte mask, in row order (a filter's selection): per-tile counts, one
 // scan, then every tile writes its ids at its offset, each wave a contiguous run per 64 rows (ballot + popcount).
-constexpr int CT_ROWS = 8192;   // rows per tile (one 256-thread workgroup)
+constexpr int CT_ROWS = kCompactTile;   // rows per tile (one 256-thread workgroup)
 
 __global__ __launch_bounds__(256) void compact_count_kernel(const unsigned char* __restrict__ mask, i64 n,
                                                             unsigned* __restrict__ cnt) {
@@ -1896,102 +1899,68 @@ __global__ __launch_bounds__(256) void run_reduce_kernel(const u64* __restrict__
 }
 
 // ---------------------------------------------------------------- host launchers
-// rows staged per scatter pass: a multiple of 1024, <= 4096, staging <= budget bytes
-inline int stage_rows(int F, int budget = 48 * 1024, int nthr = 512) {
-  const int t = (int)(budget / (14 + 8 * F)) / 256 * 256;   // wide rows (F up to 16): tiles below one row per thread
-  return std::max(256, std::min(4 * nthr, t));
-}
-
-// level-1 histogram / scatter workgroups (one per CU), >= 16 Ki rows each
-inline int agg_groups(long long n) { return (int)std::min<long long>(256, std::max<long long>(1, (n + 16383) / 16384)); }
+template <typename T>
+T* at(void* base, i64 off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
 
 // phase 0: every kernel (the device decides LOW / PART); phased launches let the host size the PART scratch only when
 // the PART path runs: 1 = init + sample + LOW, 2 = PART (its table initialised first), 3 = emit + inverse fix-up.
-// out: [reps ocap | aggs ocap*F | cnt ocap | slot_of_gid ocap | first ocap] (ocap: the groups the run may create);
+// Every size, LDS byte count and buffer offset is p's (relops_plan.h); out holds agg_ocap(p, phase) groups;
 // inv_v: [n] per-row group ids (want_inv), shared by every phase.
 template <typename VT, int OP>
-int agg_launch_t(const void* keys, const void* vals, i64 n, int F, int want_inv, int want_first, void* meta_v, void* glow_v,
-                 i64 gcap_low, void* gpart_v, i64 gcap_part, void* out_v, void* inv_v, i64 ocap, int phase, void* work_v,
-                 int pbits, int lcap_low, int lcap_part, int low_thr, int lcap_mid, i64 rs, i64 cs, hipStream_t st) {
+int agg_launch_t(const AggPlan& p, const void* keys, const void* vals, void* meta_v, void* glow_v, void* gpart_v,
+                 void* out_v, void* inv_v, int phase, void* work_v, i64 rs, i64 cs, hipStream_t st) {
+  const i64 n = p.n, gcap_low = p.glow.cap, gcap_part = p.gpart.cap;
+  const int F = p.F;
   AggMeta* meta = reinterpret_cast<AggMeta*>(meta_v);
-  // glow / gpart: [key (cap+1) | acc (cap+1)*F | cnt (cap+1) | gid (cap+1)] u64 words, preset by the caller
-  auto mk = [&](void* base, i64 cap) {
-    GTable t;
-    u64* p = reinterpret_cast<u64*>(base);
-    t.key = p;
-    t.acc = p + (cap + 1);
-    t.cnt = t.acc + (cap + 1) * F;
-    t.rmin = t.cnt + (cap + 1);
-    t.gid_of_slot = reinterpret_cast<i64*>(t.rmin + (cap + 1));
-    t.mask = (u64)(cap - 1);
-    return t;
+  auto mk = [](void* base, const AggTable& l, i64* occ) {
+    u64* w = reinterpret_cast<u64*>(base);
+    return GTable{w + l.key, w + l.acc, w + l.cnt, w + l.rmin, reinterpret_cast<i64*>(w + l.gid), (u64)(l.cap - 1), occ};
   };
-  GTable glow = mk(glow_v, gcap_low), gpart = mk(gpart_v, gcap_part);
-  glow.occ = &meta->occ_low;
-  gpart.occ = &meta->occ_part;
-  i64* ob = reinterpret_cast<i64*>(out_v);   // [reps ocap | aggs ocap*F | cnt ocap | slot_of_gid ocap | first ocap]
-  AggOut o;
-  o.reps = ob;
-  o.aggs = reinterpret_cast<u64*>(ob + ocap);
-  o.cnt = ob + ocap + ocap * F;
-  o.slot_of_gid = o.cnt + ocap;
-  o.first = o.slot_of_gid + ocap;
-  o.inv = want_inv ? reinterpret_cast<i64*>(inv_v) : nullptr;
+  const GTable glow = mk(glow_v, p.glow, &meta->occ_low), gpart = mk(gpart_v, p.gpart, &meta->occ_part);
+  const AggOutLayout ol = agg_out(agg_ocap(p, phase), F);
+  i64* ob = reinterpret_cast<i64*>(out_v);
+  const AggOut o{ob + ol.reps, reinterpret_cast<u64*>(ob + ol.aggs), ob + ol.cnt, ob + ol.slot_of_gid, ob + ol.first,
+                 p.want_inv ? reinterpret_cast<i64*>(inv_v) : nullptr};
   const u64* k = reinterpret_cast<const u64*>(keys);
   const VT* v = reinterpret_cast<const VT*>(vals);
-  const size_t lbytes_low = (size_t)lcap_low * (20 + 8 * F);
-  const size_t lbytes_part = (size_t)lcap_part * (20 + 8 * F);
 
   if (phase == 0 || phase == 1) {
     hipLaunchKernelGGL(agg_init_kernel, dim3(512), dim3(256), 0, st, reinterpret_cast<u64*>(glow_v), gcap_low,
                        phase == 0 ? reinterpret_cast<u64*>(gpart_v) : nullptr, gcap_part, F, acc_identity<VT, OP>(), meta);
-    u64* sbuf = reinterpret_cast<u64*>(meta) + sizeof(AggMeta) / 8;   // [4096] after the meta words
+    u64* sbuf = reinterpret_cast<u64*>(meta) + kMetaStructWords;   // [kSample] after the meta words
     hipLaunchKernelGGL(agg_sample_gather_kernel, dim3(kSample / 64), dim3(64), 0, st, k, n, sbuf);
-    hipLaunchKernelGGL(agg_sample_kernel, dim3(1), dim3(1024), 0, st, sbuf, n, low_thr, lcap_mid / 2, meta);
+    hipLaunchKernelGGL(agg_sample_kernel, dim3(1), dim3(1024), 0, st, sbuf, n, p.low_thr, p.lcap_mid / 2, meta);
     const int gl = (int)std::min<i64>(1024, std::max<i64>(1, (n + 2047) / 2048));
-    hipLaunchKernelGGL((agg_low_kernel<VT, OP, 256, 1>), dim3(gl), dim3(256), lbytes_low, st, k, v, n, F, rs, cs, lcap_low,
-                       glow, meta, o);
-    if (lcap_mid > 0)   // returns at once unless the sample chose the MID path
-      hipLaunchKernelGGL((agg_low_kernel<VT, OP, 1024, 2>), dim3(256), dim3(1024), (size_t)lcap_mid * (20 + 8 * F), st, k,
-                         v, n, F, rs, cs, lcap_mid, glow, meta, o);
+    hipLaunchKernelGGL((agg_low_kernel<VT, OP, 256, 1>), dim3(gl), dim3(256), (size_t)p.lds_low, st, k, v, n, F, rs, cs,
+                       p.lcap_low, glow, meta, o);
+    if (p.lcap_mid > 0)   // returns at once unless the sample chose the MID path
+      hipLaunchKernelGGL((agg_low_kernel<VT, OP, 1024, 2>), dim3(256), dim3(1024), (size_t)p.lds_mid, st, k, v, n, F, rs,
+                         cs, p.lcap_mid, glow, meta, o);
   }
   if (phase == 2)
     hipLaunchKernelGGL(agg_init_kernel, dim3(512), dim3(256), 0, st, (u64*)nullptr, gcap_low,
                        reinterpret_cast<u64*>(gpart_v), gcap_part, F, acc_identity<VT, OP>(), (AggMeta*)nullptr);
-  // PART: work buffers [hist P*G u32 | tot P | bstart P+1 | pkey n | pval n*F | prow n (i32) | qkey | qval | qrow]
-  const int P = 1 << pbits;
-  const int G = agg_groups(n);
-  const i64 rpw = (((n + G - 1) / G) + 1) & ~(i64)1;   // even: every workgroup's range starts 16-byte aligned
-  char* w = reinterpret_cast<char*>(work_v);
-  unsigned* hist = reinterpret_cast<unsigned*>(w);
-  i64* tot = reinterpret_cast<i64*>(w + (((size_t)P * G * 4 + 15) & ~(size_t)15));
-  i64* bstart = tot + P;
-  u64* pkey = reinterpret_cast<u64*>(bstart + P + 2);
-  VT* pval = reinterpret_cast<VT*>(pkey + n);
-  int* prow = reinterpret_cast<int*>(pval + n * F);
-  u64* qkey = reinterpret_cast<u64*>(prow + ((n + 1) & ~(i64)1));
-  VT* qval = reinterpret_cast<VT*>(qkey + n);
-  int* qrow = reinterpret_cast<int*>(qval + n * F);
-  if (!want_inv && !want_first) prow = qrow = nullptr;   // no row ids through the partitions
-  const int T = stage_rows(F, 96 * 1024, 1024);   // level-1 scatter: one 1024-thread workgroup per CU
-  const size_t stage_bytes = (size_t)T * (14 + 8 * F);
-  const int T2 = std::min(2048, stage_rows(F, 96 * 1024, 1024));   // bucket kernel's sub-partition tiles (2 rows / thread)
-  const size_t lds_bucket = std::max((size_t)T2 * (14 + 8 * F), lbytes_part);
   if (phase == 0 || phase == 2) {
-    hipLaunchKernelGGL(agg_hist_kernel, dim3(G), dim3(1024), (size_t)P * 4, st, k, n, rpw, pbits, hist, meta);
-    hipLaunchKernelGGL(scan_rows_kernel, dim3(P), dim3(1024), 0, st, hist, G, tot, meta, 1);
-    hipLaunchKernelGGL(scan_tot_kernel, dim3(1), dim3(1024), 0, st, tot, P, bstart, meta, 1);
-    hipLaunchKernelGGL((agg_scatter_kernel<VT>), dim3(G), dim3(1024), stage_bytes, st, k, v, rs, cs, n, F, rpw, pbits, T,
-                       hist, bstart, pkey, pval, prow, meta);
-    hipLaunchKernelGGL((agg_bucket_kernel<VT, OP>), dim3(P), dim3(1024), lds_bucket, st, pkey, pval, prow, F, lcap_part,
-                       pbits, T2, n, bstart, qkey, qval, qrow, gpart, meta, o);
+    const AggWork& w = p.work;
+    unsigned* hist = at<unsigned>(work_v, w.hist);
+    i64 *tot = at<i64>(work_v, w.tot), *bstart = at<i64>(work_v, w.bstart);
+    u64 *pkey = at<u64>(work_v, w.pkey), *qkey = at<u64>(work_v, w.qkey);
+    VT *pval = at<VT>(work_v, w.pval), *qval = at<VT>(work_v, w.qval);
+    int *prow = p.rows ? at<int>(work_v, w.prow) : nullptr, *qrow = p.rows ? at<int>(work_v, w.qrow) : nullptr;
+    hipLaunchKernelGGL(agg_hist_kernel, dim3(p.G), dim3(1024), (size_t)p.lds_hist, st, k, n, p.rpw, p.pbits, hist, meta);
+    hipLaunchKernelGGL(scan_rows_kernel, dim3(p.P), dim3(1024), 0, st, hist, p.G, tot, meta, 1);
+    hipLaunchKernelGGL(scan_tot_kernel, dim3(1), dim3(1024), 0, st, tot, p.P, bstart, meta, 1);
+    hipLaunchKernelGGL((agg_scatter_kernel<VT>), dim3(p.G), dim3(1024), (size_t)p.lds_stage, st, k, v, rs, cs, n, F, p.rpw,
+                       p.pbits, p.T, hist, bstart, pkey, pval, prow, meta);
+    hipLaunchKernelGGL((agg_bucket_kernel<VT, OP>), dim3(p.P), dim3(1024), (size_t)p.lds_bucket, st, pkey, pval, prow, F,
+                       p.lcap_part, p.pbits, p.T2, n, bstart, qkey, qval, qrow, gpart, meta, o);
   }
   if (phase == 0 || phase == 2 || phase == 3) {
     // a phase-3 (LOW) emit never reads the PART table: take_part() is false there
     hipLaunchKernelGGL((agg_emit_kernel<VT, OP>),
                        dim3((unsigned)(((phase == 3 ? gcap_low : std::max(gcap_low, gcap_part)) + 2 + 255) / 256)),
                        dim3(256), 0, st, glow, gpart, F, meta, o);
-    if (want_inv)
+    if (p.want_inv)
       hipLaunchKernelGGL(agg_fix_inv_kernel, dim3((unsigned)std::min<i64>(2048, (n + 255) / 256)), dim3(256), 0, st,
                          o.inv, n, glow.gid_of_slot, gpart.gid_of_slot, meta);
   }
@@ -2004,7 +1973,6 @@ int agg_launch_t(const void* keys, const void* vals, i64 n, int F, int want_inv,
 // Row width per column 1, 2, 4, 8 or 16 bytes (a column of wider rows is split by the host into 16-B words, a
 // multiple of them per row). blockIdx.y = column: the width switch is uniform per workgroup. Out-of-range ids write
 // zeros and raise *bad (the host checks it with the batch's other reads, never a fault).
-constexpr int kTakeCols = 48;
 struct TakeCol {
   const char* src;
   char* dst;
@@ -2051,39 +2019,21 @@ using namespace nsdb_rel;
 
 extern "C" {
 
-// Byte size of the PART work buffer for (n, F, pbits).
-long long nsdb_agg_work_bytes(long long n, int F, int pbits, int want_inv) {
-  const long long P = 1LL << pbits;
-  const long long G = agg_groups(n);
-  (void)want_inv;
-  return ((P * G * 4 + 15) & ~15LL) + 8 * (2 * P + 2) + 2 * (8 * n + 8 * n * F + 4 * (n + 1)) + 64;
-}
-
 // vt: 0 double, 1 int64; op: 0 sum, 1 min, 2 max. Value (i, f) is vals[i * vrs + f * vcs] (vrs = vcs = 0: row-major
-// [n, F]).
+// [n, F]). The buffers are the ones agg_plan(n, F, low_threshold, mid, want_inv, want_first) sizes: meta kMetaWords
+// words, glow / gpart its two tables, out agg_out(agg_ocap(plan, phase), F), work its work.total bytes.
 int nsdb_hash_aggregate(const void* keys, const void* vals, long long n, int F, int vt, int op, int want_inv,
-                        int want_first, void* meta, void* glow, long long gcap_low, void* gpart, long long gcap_part,
-                        void* out, void* inv, long long ocap, int phase, void* work, int pbits, int lcap_low,
-                        int lcap_part, int low_thr, int lcap_mid, long long vrs, long long vcs, hipStream_t st) {
+                        int want_first, long long low_threshold, int mid, void* meta, void* glow, void* gpart, void* out,
+                        void* inv, int phase, void* work, long long vrs, long long vcs, hipStream_t st) {
   if (n <= 0) return 0;
-  if (lcap_mid < 0 || (lcap_mid > 0 && ((lcap_mid & (lcap_mid - 1)) || (size_t)lcap_mid * (20 + 8 * F) > 160 * 1024 ||
-                                        gcap_low < 2LL * kMidPMax * (lcap_mid / 2))))
-    return (int)hipErrorInvalidValue;   // the MID table fits one CU's LDS; the global table holds every MID group
-  if (phase < 0 || phase > 3 || ocap <= 0 || (want_inv && inv == nullptr)) return (int)hipErrorInvalidValue;
-  if ((phase == 0 || phase == 2) && (ocap < n || work == nullptr || gpart == nullptr)) return (int)hipErrorInvalidValue;
-  if (ocap < gcap_low + 1 && ocap < n) return (int)hipErrorInvalidValue;   // every LOW group needs an output row
-  if (n >= (1LL << 31)) return (int)hipErrorInvalidValue;
-  if (F < 0 || F > 16 || pbits < 0 || pbits > 10) return (int)hipErrorInvalidValue;
-  auto pow2 = [](long long x) { return x > 0 && (x & (x - 1)) == 0; };
-  if (!pow2(gcap_low) || !pow2(gcap_part) || !pow2(lcap_low) || !pow2(lcap_part)) return (int)hipErrorInvalidValue;
-  if ((size_t)lcap_low * (20 + 8 * F) > 65536 || (size_t)lcap_part * (20 + 8 * F) > 131072) return (int)hipErrorInvalidValue;
-  if ((size_t)stage_rows(F, 96 * 1024, 1024) * (14 + 8 * F) > 131072) return (int)hipErrorInvalidValue;
-  if (F > 0 && (vrs < 0 || vcs < 0)) return (int)hipErrorInvalidValue;
+  const AggPlan p = agg_plan(n, F, low_threshold, mid != 0, want_inv != 0, want_first != 0);
+  if (agg_call_rc(p, phase, inv != nullptr, work != nullptr && gpart != nullptr, vrs, vcs) != AGG_OK)
+    return (int)hipErrorInvalidValue;
   if (vrs == 0 && vcs == 0) {   // default: row-major [n, F]
     vrs = F;
     vcs = 1;
   }
-#define NSDB_AGG(VT, OP) agg_launch_t<VT, OP>(keys, vals, n, F, want_inv, want_first, meta, glow, gcap_low, gpart, gcap_part, out, inv, ocap, phase, work, pbits, lcap_low, lcap_part, low_thr, lcap_mid, vrs, vcs, st)
+#define NSDB_AGG(VT, OP) agg_launch_t<VT, OP>(p, keys, vals, meta, glow, gpart, out, inv, phase, work, vrs, vcs, st)
   if (vt == 0) {
     if (op == 0) return NSDB_AGG(double, OP_SUM);
     if (op == 1) return NSDB_AGG(double, OP_MIN);
@@ -2113,68 +2063,28 @@ int nsdb_take_many(const void* const* src, void* const* dst, const long long* ns
   return (int)hipGetLastError();
 }
 
-// Partitioned build (tables of 2..kJPartMaxRegions regions): bytes of its workspace. Up to kJPartOneLevel regions
-// the rows are partitioned straight into regions; beyond, into kJPartCoarse coarse bins first (sh = log2 of the
-// regions per coarse bin), then split per coarse bin (jpart_sub_kernel).
-constexpr long long kJPartMaxRegions = 8192;
-constexpr unsigned kJPartOneLevel = 2048, kJPartCoarse = 256;
-static void jpart_geometry(long long n, long long cap, unsigned& P, unsigned& G, long long& rpw, int& sh) {
-  P = (unsigned)(cap >> kJRegionBits);
-  G = (unsigned)std::max<long long>(1, std::min<long long>(1024, (n + 16383) / 16384));
-  rpw = (n + G - 1) / G;
-  sh = 0;
-  if (P > kJPartOneLevel)
-    while ((P >> sh) > kJPartCoarse) ++sh;
-}
-long long nsdb_jpart_work_bytes(long long n, long long cap) {
-  unsigned P, G;
-  long long rpw;
-  int sh;
-  jpart_geometry(n, cap, P, G, rpw, sh);
-  const unsigned Pc = P >> sh;
-  const long long hist = (((long long)(Pc + 1) * G * 4) + 15) & ~15LL;
-  return hist + (long long)(Pc + 1) * 8 + (long long)(Pc + 2) * 8 + (long long)(P + 2) * 8 +
-         n * (8 + 4 + 4 + 4) + (sh ? n * 12 : 0) + 64;
-}
-
-// tab: cap + 1 slots (any content: every region and the sentinel slot are written); ctr: 3 zeroed u64 {rows of rank
-// > 0, run bump, fail}; bloom: W = cap >> bshift zeroed-or-not words (every word is written), or nullptr.
+// Partitioned build of a region table. tab: cap + 1 slots (any content: every region and the sentinel slot are
+// written); work: join_part_plan(n, cap, ...).total bytes; ctr: 3 zeroed u64 {rows of rank > 0, run bump, fail};
+// bloom: cap >> bshift zeroed-or-not words (every word is written), or nullptr.
 int nsdb_join_build_part(const void* keys, long long n, void* tab, long long cap, void* work,
                          unsigned long long* ctr, unsigned long long* bloom, int bshift, long long* perm, hipStream_t st) {
-  if (n <= 0 || cap <= (long long)kJWholeWrap || (cap & (cap - 1)) != 0 || cap < 2 * n || cap >= (1LL << 31))
-    return (int)hipErrorInvalidValue;
-  unsigned P, G;
-  long long rpw;
-  int sh;
-  jpart_geometry(n, cap, P, G, rpw, sh);
-  if (P > kJPartMaxRegions || (bloom && (bshift < 2 || bshift > kJRegionBits))) return (int)hipErrorInvalidValue;
-  const unsigned Pc = P >> sh;
-  char* w = (char*)work;
-  unsigned* hist = (unsigned*)w;
-  w += (((long long)(Pc + 1) * G * 4) + 15) & ~15LL;
-  i64* btot = (i64*)w;
-  w += (long long)(Pc + 1) * 8;
-  i64* cbase = (i64*)w;
-  w += (long long)(Pc + 2) * 8;
-  i64* bbase = (i64*)w;
-  w += (long long)(P + 2) * 8;
-  u64* ikey = (u64*)w;
-  w += n * 8;
-  int* islot = (int*)w;
-  w += n * 4;
-  unsigned* irank = (unsigned*)w;
-  w += n * 4;
-  unsigned* irow = (unsigned*)w;
-  w += n * 4;
-  u64* ikey1 = sh ? (u64*)w : ikey;
-  unsigned* irow1 = sh ? (unsigned*)(w + n * 8) : irow;
+  const JoinPartPlan p = join_part_plan(n, cap, bloom != nullptr, bshift);
+  if (p.rc != JOIN_OK) return (int)hipErrorInvalidValue;
+  const unsigned P = p.P, G = p.G, Pc = p.Pc;
+  const int sh = p.sh;
+  const i64 rpw = p.rpw;
+  unsigned* hist = at<unsigned>(work, p.hist);
+  i64 *btot = at<i64>(work, p.btot), *cbase = at<i64>(work, p.cbase), *bbase = at<i64>(work, p.bbase);
+  u64 *ikey = at<u64>(work, p.ikey), *ikey1 = at<u64>(work, p.ikey1);
+  int* islot = at<int>(work, p.islot);
+  unsigned *irank = at<unsigned>(work, p.irank), *irow = at<unsigned>(work, p.irow), *irow1 = at<unsigned>(work, p.irow1);
   const u64 mask = (u64)(cap - 1);
-  const size_t lds = (size_t)(Pc + 1) * 4;
+  const size_t lds = (size_t)p.lds_hist;
   hipLaunchKernelGGL(jpart_hist_kernel, dim3(G), dim3(kJPartThreads), lds, st, (const u64*)keys, (i64)n, (i64)rpw, mask,
                      Pc, sh, hist, (JSlot*)tab);
   hipLaunchKernelGGL(jpart_colscan_kernel, dim3((Pc + 1 + 255) / 256), dim3(256), 0, st, hist, G, Pc + 1, btot);
   hipLaunchKernelGGL(jpart_totscan_kernel, dim3(1), dim3(1024), 0, st, (const i64*)btot, Pc + 1, sh ? cbase : bbase);
-  if (sh && Pc + 1 <= (unsigned)kJStageBins)
+  if (p.staged)
     hipLaunchKernelGGL(jpart_scatter_staged_kernel, dim3(G), dim3(kJPartThreads), 0, st, (const u64*)keys, (i64)n,
                        (i64)rpw, mask, Pc, sh, (const unsigned*)hist, (const i64*)cbase, ikey1, irow1);
   else
@@ -2227,14 +2137,12 @@ int nsdb_join_perm(const int* row_slot, const unsigned* row_rank, long long n, c
   return (int)hipGetLastError();
 }
 
-long long nsdb_join_tiles(long long m) { return (m + kJTile - 1) / kJTile; }
-
-// cnt / pay [m] u32, tile_sum [nsdb_join_tiles(m)] i64
+// cnt / pay [m] u32, tile_sum [join_tiles(m)] i64
 int nsdb_join_probe(const void* keys, long long m, const void* tab, long long cap, unsigned* cnt, unsigned* pay,
                     long long* tile_sum, const unsigned long long* bloom, int bshift, hipStream_t st) {
   if (m <= 0) return 0;
   if (cap <= 0 || (cap & (cap - 1)) != 0) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(join_probe_kernel, dim3((unsigned)nsdb_join_tiles(m)), dim3(256), 0, st, (const u64*)keys, m,
+  hipLaunchKernelGGL(join_probe_kernel, dim3((unsigned)join_tiles(m)), dim3(256), 0, st, (const u64*)keys, m,
                      (const JSlot*)tab, (u64)(cap - 1), cnt, pay, tile_sum, bloom, bshift);
   return (int)hipGetLastError();
 }
@@ -2242,10 +2150,8 @@ int nsdb_join_probe(const void* keys, long long m, const void* tab, long long ca
 // the table's probe filter: W words (a power of two <= cap), bloom zeroed by the caller
 int nsdb_join_bloom(const void* tab, long long cap, long long W, unsigned long long* bloom, hipStream_t st) {
   if (W <= 0 || (W & (W - 1)) != 0 || W > cap || (cap & (cap - 1)) != 0) return (int)hipErrorInvalidValue;
-  int shift = 0;
-  while ((W << shift) < cap) ++shift;
   hipLaunchKernelGGL(join_bloom_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, (const JSlot*)tab,
-                     (u64)(cap - 1), shift, (i64)W, bloom);
+                     (u64)(cap - 1), join_filter_shift(cap, W), (i64)W, bloom);
   return (int)hipGetLastError();
 }
 
@@ -2253,43 +2159,32 @@ int nsdb_join_bloom(const void* tab, long long cap, long long W, unsigned long l
 int nsdb_join_expand(const unsigned* cnt, const unsigned* pay, long long m, const long long* tile_base,
                      const long long* perm, long long* bidx, long long* pidx, hipStream_t st) {
   if (m <= 0) return 0;
-  hipLaunchKernelGGL(join_expand_kernel, dim3((unsigned)nsdb_join_tiles(m)), dim3(256), 0, st, cnt, pay, m, tile_base,
+  hipLaunchKernelGGL(join_expand_kernel, dim3((unsigned)join_tiles(m)), dim3(256), 0, st, cnt, pay, m, tile_base,
                      perm, bidx, pidx);
   return (int)hipGetLastError();
 }
 
-// Stable partition permutation: dest [n] in [0, P), P <= 2048. work: hist P*G u32 + tot P i64 + bstart P+1 i64.
-long long nsdb_part_work_bytes(long long n, int P) {
-  const long long G = std::min<long long>(256, std::max<long long>(1, (n + 16383) / 16384));
-  return ((P * G * 4 + 15) & ~15LL) + 8 * (2 * P + 1) + 64;
-}
-
+// Stable partition permutation: dest [n] in [0, P), P <= kPartMaxP. work: part_plan(n, P).total bytes.
 int nsdb_partition_perm(const long long* dest, long long n, int P, void* work, long long* perm, long long* counts,
                         hipStream_t st) {
   if (n <= 0) return 0;
-  if (P <= 0 || P > 2048 || n >= (1LL << 31)) return (int)hipErrorInvalidValue;
-  const int G = (int)std::min<long long>(256, std::max<long long>(1, (n + 16383) / 16384));
-  const long long rpw = (n + G - 1) / G;
-  const size_t lds = (size_t)P * 4 * 17;
-  if (lds > 163840) return (int)hipErrorInvalidValue;
-  char* w = reinterpret_cast<char*>(work);
-  unsigned* hist = reinterpret_cast<unsigned*>(w);
-  long long* tot = reinterpret_cast<long long*>(w + (((size_t)P * G * 4 + 15) & ~(size_t)15));
-  long long* bstart = tot + P;
-  hipLaunchKernelGGL(part_hist_kernel, dim3(G), dim3(1024), (size_t)P * 4, st, dest, n, rpw, P, hist);
-  hipLaunchKernelGGL(scan_rows_kernel, dim3(P), dim3(1024), 0, st, hist, G, tot, (const AggMeta*)nullptr, 0);
+  const PartPlan p = part_plan(n, P);
+  if (p.rc != PART_OK) return (int)hipErrorInvalidValue;
+  unsigned* hist = at<unsigned>(work, p.hist);
+  long long *tot = at<long long>(work, p.tot), *bstart = at<long long>(work, p.bstart);
+  hipLaunchKernelGGL(part_hist_kernel, dim3(p.G), dim3(1024), (size_t)p.lds_hist, st, dest, n, p.rpw, P, hist);
+  hipLaunchKernelGGL(scan_rows_kernel, dim3(P), dim3(1024), 0, st, hist, p.G, tot, (const AggMeta*)nullptr, 0);
   hipLaunchKernelGGL(scan_tot_kernel, dim3(1), dim3(1024), 0, st, tot, P, bstart, (AggMeta*)nullptr, 0);
-  hipLaunchKernelGGL(part_scatter_kernel, dim3(G), dim3(1024), lds, st, dest, n, rpw, P, hist, bstart, perm);
+  hipLaunchKernelGGL(part_scatter_kernel, dim3(p.G), dim3(1024), (size_t)p.lds_scatter, st, dest, n, p.rpw, P, hist, bstart,
+                     perm);
   if (counts) (void)hipMemcpyAsync(counts, tot, sizeof(long long) * P, hipMemcpyDeviceToDevice, st);
   return (int)hipGetLastError();
 }
 
-// Tiles of a compaction and its scratch (tile counts u32 + offsets i64 [T + 1]).
-long long nsdb_compact_tiles(long long n) { return (n + nsdb_rel::CT_ROWS - 1) / nsdb_rel::CT_ROWS; }
-
+// Compaction scratch: tile counts u32 [T] + offsets i64 [T + 1], T = compact_tiles(n).
 // Phase 1: tile counts + offsets (off[T] = the number of set rows, which the caller reads to size the output).
 int nsdb_compact_count(const unsigned char* mask, long long n, unsigned* cnt, long long* off, hipStream_t st) {
-  const long long T = nsdb_compact_tiles(n);
+  const long long T = compact_tiles(n);
   if (T <= 0 || T > (1LL << 30) || (reinterpret_cast<uintptr_t>(mask) & 15)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)T), dim3(256), 0, st, mask, n, cnt);
   hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, cnt, (int)T, off);
@@ -2298,7 +2193,7 @@ int nsdb_compact_count(const unsigned char* mask, long long n, unsigned* cnt, lo
 
 // Phase 2: the row ids, in order, at out[0 .. off[T]).
 int nsdb_compact_write(const unsigned char* mask, long long n, const long long* off, long long* out, hipStream_t st) {
-  const long long T = nsdb_compact_tiles(n);
+  const long long T = compact_tiles(n);
   if (T <= 0) return 0;
   hipLaunchKernelGGL(compact_write_kernel, dim3((unsigned)T), dim3(256), 0, st, mask, n, off, out);
   return (int)hipGetLastError();
@@ -2307,7 +2202,7 @@ int nsdb_compact_write(const unsigned char* mask, long long n, const long long* 
 // Clustered-key aggregation, phase 1: run heads per tile and the descending-step flag. off has T + 2 words:
 // off[T] = the number of runs (groups), off[T + 1] = nonzero when the keys are not ordered (the caller reads both).
 int nsdb_run_count(const void* keys, long long n, unsigned* cnt, long long* off, hipStream_t st) {
-  const long long T = nsdb_compact_tiles(n);
+  const long long T = compact_tiles(n);
   if (T <= 0 || T > (1LL << 30)) return (int)hipErrorInvalidValue;
   hipMemsetAsync(off + T + 1, 0, sizeof(long long), st);
   hipLaunchKernelGGL(run_count_kernel, dim3((unsigned)T), dim3(256), 0, st, reinterpret_cast<const u64*>(keys), n, cnt,
@@ -2320,7 +2215,7 @@ int nsdb_run_count(const void* keys, long long n, unsigned* cnt, long long* off,
 int nsdb_run_reduce(const void* keys, const void* vals, long long rs, long long cs, int F, int vt, int op, long long n,
                     const long long* off, long long G, long long* heads, long long* okey, void* oagg, long long* ocnt,
                     hipStream_t st) {
-  const long long T = nsdb_compact_tiles(n);
+  const long long T = compact_tiles(n);
   if (T <= 0) return 0;
   const u64* k = reinterpret_cast<const u64*>(keys);
   const unsigned long long* desc = reinterpret_cast<const unsigned long long*>(off + T + 1);

@@ -10,23 +10,21 @@
 #include <tuple>
 #include <vector>
 
+#include "relops_plan.h"
+
 typedef long long ll;
 template <typename T> ll* LL(T* p) { return reinterpret_cast<ll*>(p); }
 
 extern "C" {
-long long nsdb_agg_work_bytes(long long n, int F, int pbits, int want_inv);
 int nsdb_hash_aggregate(const void* keys, const void* vals, long long n, int F, int vt, int op, int want_inv,
-                        int want_first, void* meta, void* glow, long long gcap_low, void* gpart, long long gcap_part,
-                        void* out, void* inv, long long ocap, int phase, void* work, int pbits, int lcap_low,
-                        int lcap_part, int low_thr, int lcap_mid, long long vrs, long long vcs, hipStream_t st);
+                        int want_first, long long low_threshold, int mid, void* meta, void* glow, void* gpart, void* out,
+                        void* inv, int phase, void* work, long long vrs, long long vcs, hipStream_t st);
 int nsdb_join_insert(const void* keys, long long n, void* tab, long long cap, int* row_slot, unsigned* row_rank,
                      unsigned long long* ndup, unsigned* fail, hipStream_t st);
-long long nsdb_jpart_work_bytes(long long n, long long cap);
 int nsdb_join_build_part(const void* keys, long long n, void* tab, long long cap, void* work,
                          unsigned long long* ctr, unsigned long long* bloom, int bshift, long long* perm, hipStream_t st);
 int nsdb_join_perm(const int* row_slot, const unsigned* row_rank, long long n, const unsigned long long* ndup,
                    unsigned long long* bump, void* tab, long long cap, long long* perm, hipStream_t st);
-long long nsdb_join_tiles(long long m);
 int nsdb_join_probe(const void* keys, long long m, const void* tab, long long cap, unsigned* cnt, unsigned* pay,
                     long long* tile_sum, const unsigned long long* bloom, int bshift, hipStream_t st);
 int nsdb_join_bloom(const void* tab, long long cap, long long W, unsigned long long* bloom, hipStream_t st);
@@ -35,9 +33,7 @@ int nsdb_take_many(const void* const* src, void* const* dst, const long long* ns
                    int ncols, const long long* idx, long long n, int* bad, hipStream_t st);
 int nsdb_join_expand(const unsigned* cnt, const unsigned* pay, long long m, const long long* tile_base,
                      const long long* perm, long long* bidx, long long* pidx, hipStream_t st);
-long long nsdb_part_work_bytes(long long n, int P);
 int nsdb_mix64(const void* x, const void* y, void* out, long long n, hipStream_t st);
-long long nsdb_compact_tiles(long long n);
 int nsdb_compact_count(const unsigned char* mask, long long n, unsigned* cnt, long long* off, hipStream_t st);
 int nsdb_compact_write(const unsigned char* mask, long long n, const long long* off, long long* out, hipStream_t st);
 int nsdb_partition_perm(const long long* dest, long long n, int P, void* work, long long* perm, long long* counts,
@@ -70,19 +66,44 @@ void rc_ok(int rc, const char* what) {
   TORCH_CHECK(rc == 0, what, " failed with code ", rc, " (", hipGetErrorString((hipError_t)(rc > 0 ? rc : 0)), ")");
 }
 
-int64_t pow2_at_least(int64_t x) {
-  int64_t c = 1;
-  while (c < x) c <<= 1;
-  return c;
-}
-int64_t pow2_at_most(int64_t x) {
-  int64_t c = 1;
-  while (c * 2 <= x) c <<= 1;
-  return c;
+int op_code(const std::string& op) {
+  const int opc = op == "sum" ? 0 : op == "min" ? 1 : op == "max" ? 2 : -1;
+  TORCH_CHECK(opc >= 0, "op must be sum, min or max");
+  return opc;
 }
 
-// Word offsets of the AggMeta fields (relops.hip): est, low, ng_low, ng_part, fail_low, fail_part, ...
-constexpr int kMetaWords = 16 + 4096;   // AggMeta + the sampled keys (relops.hip agg_sample_*)
+// The value columns of a group-by: [n] or [n, F] float64 / int64 on the keys' device, or none (F = 0).
+struct AggVals {
+  torch::Tensor v;
+  int F = 0, vt = 0;             // vt: 0 double, 1 int64
+  int64_t vrs = 0, vcs = 0;      // element strides of a row / a column
+  c10::ScalarType dtype = torch::kFloat64;
+  const void* ptr() const { return F ? v.data_ptr() : nullptr; }
+};
+// in_place: row-major [n, F] or column-major (the transpose of a contiguous [F, n] stack) are read where they are,
+// anything else is made contiguous; otherwise any strides are taken as they come
+AggVals agg_vals(const c10::optional<torch::Tensor>& vals, const torch::Tensor& keys, bool in_place) {
+  AggVals a;
+  if (!vals.has_value() || !vals->defined() || vals->numel() == 0) return a;
+  const int64_t n = keys.numel();
+  a.v = *vals;
+  TORCH_CHECK(a.v.is_cuda() && a.v.device() == keys.device(), "vals must be on the keys' device");
+  TORCH_CHECK(a.v.scalar_type() == torch::kFloat64 || a.v.scalar_type() == torch::kInt64, "vals must be float64 or int64");
+  if (a.v.dim() == 1) a.v = a.v.unsqueeze(1);
+  TORCH_CHECK(a.v.dim() == 2 && a.v.size(0) == n, "vals must be [n] or [n, F]");
+  a.vrs = a.v.stride(0);
+  a.vcs = a.v.stride(1);
+  if (in_place) {
+    const bool colmajor = a.v.size(1) > 1 && a.v.stride(0) == 1 && a.v.stride(1) >= n;
+    if (!colmajor) a.v = a.v.contiguous();
+    a.vrs = a.v.size(1) > 1 ? a.v.stride(0) : 1;
+    a.vcs = a.v.size(1) > 1 ? a.v.stride(1) : 1;
+  }
+  a.F = (int)a.v.size(1);
+  a.vt = a.v.scalar_type() == torch::kInt64 ? 1 : 0;
+  a.dtype = a.v.scalar_type();
+  return a;
+}
 
 // Group n int64 keys and reduce F value columns per group on the device.
 //   vals: [n, F] float64 or int64 (or None / F == 0: counts only); op: "sum" | "min" | "max".
@@ -92,11 +113,12 @@ constexpr int kMetaWords = 16 + 4096;   // AggMeta + the sampled keys (relops.hi
 // invalid, fall back), distinct keys in the 4096-row sample, scratch bytes used]. low_threshold: largest estimated
 // group count for the LOW path (0: automatic).
 //
-// Scratch is sized for the path that runs. Phase 1 (sample + LOW) needs O(groups) words: the LOW global table and an
-// output of gcap_low + 1 groups. Only when the device reports that the LOW path did not take the rows (one host read,
-// which the LOW path needs anyway for its group count) are the PART buffers allocated — about 2 (12 + 8 F) n bytes of
-// partitioned rows plus an n-group output — and `scratch(+bytes)` / `scratch(-bytes)` (a Python callable, e.g. the
-// storage manager's device-budget accounting) is told before they are allocated and after they are released.
+// Every buffer is sized by agg_plan (relops_plan.h), for the path that runs. Phase 1 (sample + LOW) needs O(groups)
+// words: the LOW global table and an output of ocap_low groups. Only when the device reports that the LOW path did not
+// take the rows (one host read, which the LOW path needs anyway for its group count) are the PART buffers allocated —
+// about 2 (12 + 8 F) n bytes of partitioned rows plus an n-group output — and `scratch(+bytes)` / `scratch(-bytes)` (a
+// Python callable, e.g. the storage manager's device-budget accounting) is told before they are allocated and after
+// they are released.
 std::vector<torch::Tensor> hash_aggregate(torch::Tensor keys, c10::optional<torch::Tensor> vals, const std::string& op,
                                           bool want_inv, int64_t low_threshold, bool want_first,
                                           pybind11::object scratch) {
@@ -105,107 +127,68 @@ std::vector<torch::Tensor> hash_aggregate(torch::Tensor keys, c10::optional<torc
   keys = keys.contiguous();
   const int64_t n = keys.numel();
   TORCH_CHECK(n < (int64_t(1) << 31), "hash_aggregate: at most 2^31 - 1 rows per call (the caller chunks)");
-  int opc = op == "sum" ? 0 : op == "min" ? 1 : op == "max" ? 2 : -1;
-  TORCH_CHECK(opc >= 0, "op must be sum, min or max");
-  int F = 0, vt = 0;
-  int64_t vrs = 0, vcs = 0;
-  torch::Tensor v;
-  auto vdtype = torch::kFloat64;
-  if (vals.has_value() && vals->defined() && vals->numel() > 0) {
-    v = *vals;
-    TORCH_CHECK(v.is_cuda() && v.device() == keys.device(), "vals must be on the keys' device");
-    TORCH_CHECK(v.scalar_type() == torch::kFloat64 || v.scalar_type() == torch::kInt64, "vals must be float64 or int64");
-    if (v.dim() == 1) v = v.unsqueeze(1);
-    TORCH_CHECK(v.dim() == 2 && v.size(0) == n, "vals must be [n] or [n, F]");
-    // row-major [n, F] or column-major (the transpose of a contiguous [F, n] stack) are read in place
-    const bool colmajor = v.size(1) > 1 && v.stride(0) == 1 && v.stride(1) >= n;
-    if (!colmajor) v = v.contiguous();
-    vrs = v.size(1) > 1 ? v.stride(0) : 1;
-    vcs = v.size(1) > 1 ? v.stride(1) : 1;
-    F = (int)v.size(1);
-    TORCH_CHECK(F <= 16, "at most 16 value columns");
-    vt = v.scalar_type() == torch::kInt64 ? 1 : 0;
-    vdtype = v.scalar_type();
-  }
+  const int opc = op_code(op);
+  const AggVals a = agg_vals(vals, keys, true);
+  const int F = a.F;
+  TORCH_CHECK(F <= 16, "at most 16 value columns");
   auto i64 = keys.options().dtype(torch::kInt64);
   if (n == 0) {
-    return {torch::empty({0}, i64), torch::empty({0, F}, keys.options().dtype(vdtype)), torch::empty({0}, i64),
+    return {torch::empty({0}, i64), torch::empty({0, F}, keys.options().dtype(a.dtype)), torch::empty({0}, i64),
             torch::empty({0}, i64), torch::empty({0}, i64), torch::tensor({0, 0, 1, 0, 0}, torch::kInt64)};
   }
-  // LDS tables: LOW <= 64 KiB (two workgroups per CU), PART <= 128 KiB. PART: level-1 buckets = one per CU
-  // (256) once there are >= 2048 rows per bucket; each bucket workgroup splits its bucket further on the device
-  // from the sampled distinct-key estimate (relops.hip agg_bucket_kernel), so no host decision needs the data.
-  const int64_t entry = 20 + 8 * F;
-  const int64_t lcap_low = std::min<int64_t>(1024, pow2_at_most(65536 / entry));   // <= 36 KB: 4+ LOW workgroups per CU
-  const int64_t lcap_part = std::min<int64_t>(4096, pow2_at_most(131072 / entry));
-  int pbits = 0;
-  while (pbits < 8 && (n >> (pbits + 1)) >= 2048) ++pbits;
-  // MID path (relops.hip agg_low_kernel MODE 2): up to 8 hash partitions of the key space, each one CU-sized LDS
-  // table of lcap_mid slots (half full at most); 0 disables it. The LOW global table then holds every MID group.
-  // (an explicit low_threshold pins the LOW / PART boundary: no MID path then)
-  const int64_t lcap_mid =
-      g_agg_mid && low_threshold <= 0 ? std::min<int64_t>(4096, pow2_at_most(160 * 1024 / entry)) : 0;
-  const int64_t gcap_low = std::max<int64_t>(4 * lcap_low, lcap_mid > 0 ? 2 * 8 * (lcap_mid / 2) : 0);
-  // overflow table of the PART path (keys whose LDS probe window filled): a miss-sized estimate only
-  const int64_t gcap_part = std::max<int64_t>(4096, std::min<int64_t>(pow2_at_least(2 * n), int64_t(1) << 17));
-  const int64_t thr = low_threshold > 0 ? low_threshold : lcap_low / 4;
-
-  auto meta = torch::empty({kMetaWords}, i64);
-  auto glow = torch::empty({(gcap_low + 1) * (4 + F)}, i64);
+  const nsdb::AggPlan p = nsdb::agg_plan(n, F, low_threshold, g_agg_mid, want_inv, want_first);
+  TORCH_CHECK(p.rc == nsdb::AGG_OK, "hash_aggregate: bad plan (code ", p.rc, ")");
+  auto meta = torch::empty({nsdb::kMetaWords}, i64);
+  auto glow = torch::empty({p.glow.words}, i64);
   auto inv = want_inv ? torch::empty({n}, i64) : torch::empty({0}, i64);
-  const int64_t ocap_low = std::min<int64_t>(n, gcap_low + 1);
-  auto out = torch::empty({ocap_low * (4 + F)}, i64);
-  int64_t ocap = ocap_low;
+  auto out = torch::empty({nsdb::agg_out(p.ocap_low, F).words}, i64);
   auto launch = [&](int phase, void* gpart, void* work) {
-    rc_ok(nsdb_hash_aggregate(keys.data_ptr(), F ? v.data_ptr() : nullptr, n, F, vt, opc, want_inv ? 1 : 0,
-                              want_first ? 1 : 0, meta.data_ptr(), glow.data_ptr(), gcap_low, gpart, gcap_part,
-                              out.data_ptr(), want_inv ? inv.data_ptr() : nullptr, ocap, phase, work, pbits,
-                              (int)lcap_low, (int)lcap_part, (int)thr, (int)lcap_mid, (long long)vrs, (long long)vcs,
+    rc_ok(nsdb_hash_aggregate(keys.data_ptr(), a.ptr(), n, F, a.vt, opc, want_inv ? 1 : 0, want_first ? 1 : 0,
+                              low_threshold, g_agg_mid ? 1 : 0, meta.data_ptr(), glow.data_ptr(), gpart, out.data_ptr(),
+                              want_inv ? inv.data_ptr() : nullptr, phase, work, (long long)a.vrs, (long long)a.vcs,
                               stream()),
           "hash_aggregate");
   };
+  auto read_meta = [&]() { return meta.narrow(0, 0, nsdb::kMetaStructWords).cpu(); };   // the host read: counts and flags
   launch(1, nullptr, nullptr);
-  auto m = meta.narrow(0, 0, 16).cpu();   // the host read: group count and path flags
+  auto m = read_meta();
   const ll* mp = LL(m.data_ptr<int64_t>());
-  // AggMeta words: 0 est, 1 low, 2 ng_low, 3 ng_part, 4 fail_low, 5 fail_part
-  const bool low_ok = mp[1] != 0 && mp[4] == 0;
-  int64_t scratch_bytes = (int64_t)(meta.numel() + glow.numel() + inv.numel() + out.numel()) * 8;
+  const bool low_ok = mp[nsdb::kMetaLow] != 0 && mp[nsdb::kMetaFailLow] == 0;
+  int64_t scratch_bytes = p.phase1_bytes;
   bool ok = true;
   int64_t g = 0;
   if (low_ok) {
     launch(3, nullptr, nullptr);
-    g = (int64_t)mp[2];
+    g = (int64_t)mp[nsdb::kMetaNgLow];
   } else {
-    const int64_t wbytes = nsdb_agg_work_bytes(n, F, pbits, want_inv ? 1 : 0);
-    const int64_t part_bytes = ((gcap_part + 1) * (4 + F) + n * (4 + F)) * 8 + wbytes;
-    if (!scratch.is_none()) scratch(part_bytes);
+    if (!scratch.is_none()) scratch(p.part_bytes);
     try {
-      auto gpart = torch::empty({(gcap_part + 1) * (4 + F)}, i64);
-      auto work = torch::empty({(wbytes + 7) / 8}, i64);
-      ocap = n;
-      out = torch::empty({n * (4 + F)}, i64);
+      auto gpart = torch::empty({p.gpart.words}, i64);
+      auto work = torch::empty({(p.work.total + 7) / 8}, i64);
+      out = torch::empty({nsdb::agg_out(n, F).words}, i64);
       launch(2, gpart.data_ptr(), work.data_ptr());
-      auto m2 = meta.narrow(0, 0, 16).cpu();
+      auto m2 = read_meta();
       const ll* mp2 = LL(m2.data_ptr<int64_t>());
-      g = (int64_t)mp2[3];
-      ok = mp2[5] == 0;
-      scratch_bytes += part_bytes - (int64_t)ocap_low * (4 + F) * 8;
+      g = (int64_t)mp2[nsdb::kMetaNgPart];
+      ok = mp2[nsdb::kMetaFailPart] == 0;
+      scratch_bytes += p.part_bytes - 8 * nsdb::agg_out(p.ocap_low, F).words;
     } catch (...) {
-      if (!scratch.is_none()) scratch(-part_bytes);
+      if (!scratch.is_none()) scratch(-p.part_bytes);
       throw;
     }
-    if (!scratch.is_none()) scratch(-part_bytes);
+    if (!scratch.is_none()) scratch(-p.part_bytes);
   }
-  auto status = torch::tensor({(int64_t)g, (int64_t)(low_ok ? 0 : 1), (int64_t)(ok ? 1 : 0), (int64_t)mp[0],
+  auto status = torch::tensor({(int64_t)g, (int64_t)(low_ok ? 0 : 1), (int64_t)(ok ? 1 : 0), (int64_t)mp[nsdb::kMetaEst],
                                scratch_bytes}, torch::kInt64);
   if (!ok) return {torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), status};
-  auto reps = out.narrow(0, 0, g);
-  auto aggs = out.narrow(0, ocap, g * F).view({g, F});
-  if (vt == 0) aggs = aggs.view(torch::kFloat64);
-  auto cnt = out.narrow(0, ocap + ocap * F, g);
-  auto first = out.narrow(0, ocap * (3 + F), g);
+  const nsdb::AggOutLayout o = nsdb::agg_out(low_ok ? p.ocap_low : n, F);
+  auto reps = out.narrow(0, o.reps, g);
+  auto aggs = out.narrow(0, o.aggs, g * F).view({g, F});
+  if (a.vt == 0) aggs = aggs.view(torch::kFloat64);
+  auto cnt = out.narrow(0, o.cnt, g);
+  auto first = out.narrow(0, o.first, g);
   // the views keep the whole ocap-row buffer alive: copy small results out of a large one
-  if (ocap > ocap_low && g * 4 < ocap) {
+  if (o.ocap > p.ocap_low && g * 4 < o.ocap) {
     reps = reps.clone();
     aggs = aggs.clone();
     cnt = cnt.clone();
@@ -214,53 +197,38 @@ std::vector<torch::Tensor> hash_aggregate(torch::Tensor keys, c10::optional<torc
   return {reps, aggs, cnt, first, inv, status};
 }
 
+nsdb::JoinPlan join_plan_now(int64_t n, int64_t cap_override) {
+  return nsdb::join_plan(n, cap_override, g_join_bloom, g_join_bloom_min_bytes, g_join_bloom_max_bytes, g_join_part);
+}
+
 // Join build: returns (table [cap+1, 2] i64 of 16-byte slots {key, cnt | pay << 32}, perm [n] i64: the CSR runs of
 // repeated keys; untouched when no key repeats, every payload being the build row itself). No host read.
+// join_plan (relops_plan.h) decides the load factor, the table kind, the probe filter and the workspace. A region
+// table is built region by region in LDS and checked once on the host for a region left without an empty slot (a hash
+// pile-up far outside the load's statistics), in which case it doubles and is rebuilt. Smaller ones: the global
+// insert, whole-table linear probing.
 std::vector<torch::Tensor> join_build(torch::Tensor keys) {
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.dim() == 1, "keys: 1-D int64 GPU tensor");
   keys = keys.contiguous();
   const int64_t n = keys.numel();
   TORCH_CHECK(n < (int64_t(1) << 29), "join_build: at most 2^29 build rows per table");
-  // load factor: <= 1/8 for builds up to 256 k rows (a <= 64 MiB table: a probe of an ABSENT key — most probe rows of
-  // a selective join, TPC-H Q17's 60 M lineitems against ~2 k parts — expects ~1.1 slot reads instead of ~2.5 at 1/2),
-  // <= 1/4 up to 4 M rows, <= 1/2 beyond
-  const int64_t f = n <= (int64_t(1) << 18) ? 8 : (n <= (int64_t(1) << 22) ? 4 : 2);
-  int64_t cap = pow2_at_least(std::max<int64_t>(1024, f * n));
   auto i64 = keys.options().dtype(torch::kInt64);
-  // Tables of more than 2^22 slots: chains wrap inside regions of kJRegion = 4096 slots (relops.hip), the table is
-  // built region by region in LDS (join_build_part) and checked once on the host for a region left without an empty
-  // slot (a hash pile-up far outside the load's statistics), in which case it doubles and is rebuilt. Smaller ones:
-  // the global insert, whole-table linear probing.
-  constexpr int64_t R = 4096, kMaxRegions = 8192, kWhole = int64_t(1) << 22;   // relops.hip kJRegion, kJWholeWrap
+  int64_t cap_override = 0;
   for (int attempt = 0;; ++attempt) {
+    const nsdb::JoinPlan p = join_plan_now(n, cap_override);
+    const int64_t cap = p.cap;
     auto tab = torch::empty({cap + 1, 2}, i64);
     auto ctr = torch::zeros({3}, i64);   // [repeated-key rows, run bump counter, fail]
     auto* c = reinterpret_cast<unsigned long long*>(ctr.data_ptr<int64_t>());
     auto perm = torch::empty({n}, i64);
-    // probe filter for tables past the L2 (> 4 MiB of slots): ~16 filter bits per build row, one word per 2^shift slots
-    torch::Tensor bloom = torch::empty({0}, i64);
-    int bshift = -1;
-    // ... while the filter itself stays L2-sized (<= 4 MiB: builds up to ~2 M rows). A larger one sits in the MALL
-    // next to the table, and its word is a second dependent far read for every probe that matches (16 M-row build,
-    // 90 % matching probes: 0.89 ms with the filter, 0.70 without, profiles/r6_join)
-    if (g_join_bloom && cap * 16 > g_join_bloom_min_bytes &&
-        std::min<int64_t>(cap, pow2_at_least(std::max<int64_t>(64, (16 * n + 63) / 64))) * 8 <= g_join_bloom_max_bytes) {
-      const int64_t W = std::min<int64_t>(cap, pow2_at_least(std::max<int64_t>(64, (16 * n + 63) / 64)));
-      bshift = 0;
-      while ((W << bshift) < cap) ++bshift;
-      bloom = torch::empty({W}, i64);
-    }
-    const bool regions = cap > kWhole;                        // chains wrap inside 4096-slot regions
-    const bool part = regions && (cap / R) <= kMaxRegions && g_join_part;
-    bool bloom_done = false;
-    if (part) {
-      const bool fold = bshift >= 2 && bshift <= 12;          // filter words written with their region
-      auto work = torch::empty({(nsdb_jpart_work_bytes(n, cap) + 7) / 8}, i64);
-      rc_ok(nsdb_join_build_part(keys.data_ptr(), n, tab.data_ptr(), cap, work.data_ptr(), c,
-                                 fold ? reinterpret_cast<unsigned long long*>(bloom.data_ptr<int64_t>()) : nullptr,
-                                 bshift, LL(perm.data_ptr<int64_t>()), stream()),
+    auto bloom = torch::empty({p.W}, i64);
+    auto* bp = reinterpret_cast<unsigned long long*>(bloom.data_ptr<int64_t>());
+    if (p.part) {
+      TORCH_CHECK(p.work.rc == nsdb::JOIN_OK, "join_build: bad plan (code ", p.work.rc, ")");
+      auto work = torch::empty({(p.work.total + 7) / 8}, i64);
+      rc_ok(nsdb_join_build_part(keys.data_ptr(), n, tab.data_ptr(), cap, work.data_ptr(), c, p.fold ? bp : nullptr,
+                                 p.bshift, LL(perm.data_ptr<int64_t>()), stream()),
             "join_build_part");
-      bloom_done = fold;
     } else {
       rc_ok(nsdb_join_init(tab.data_ptr(), cap, stream()), "join_init");
       auto row_slot = torch::empty({n}, keys.options().dtype(torch::kInt32));
@@ -274,23 +242,21 @@ std::vector<torch::Tensor> join_build(torch::Tensor keys) {
                            c + 1, tab.data_ptr(), cap, LL(perm.data_ptr<int64_t>()), stream()),
             "join_perm");
     }
-    if (bshift >= 0 && !bloom_done) {
+    if (p.W > 0 && !p.fold) {
       bloom.zero_();
-      rc_ok(nsdb_join_bloom(tab.data_ptr(), cap, bloom.numel(),
-                            reinterpret_cast<unsigned long long*>(bloom.data_ptr<int64_t>()), stream()),
-            "join_bloom");
+      rc_ok(nsdb_join_bloom(tab.data_ptr(), cap, p.W, bp, stream()), "join_bloom");
     }
     // Region tables (builds past ~1 M rows) read {fail, largest extra-row count} in one transfer: a region left
     // without an empty slot is rebuilt larger; the count is the table's max multiplicity - 1 (JoinTable
     // .max_multiplicity, which sizes the fused probes' output regions, needs no read of its own). Whole-table tables
     // cannot fill (load <= 1/2): no host read.
     torch::Tensor stat = torch::empty({0}, i64);
-    if (regions) {
+    if (p.regions) {
       stat = torch::stack({ctr[2], tab.select(1, 1).bitwise_and(0xFFFFFFFFLL).max()}).cpu();
       if (stat[0].item<int64_t>() != 0) {                    // a region without an empty slot: rebuild larger
         TORCH_CHECK(attempt < 2 && cap * 2 < (int64_t(1) << 31),
                     "join_build: hash regions overflow even at ", cap, " slots for ", n, " rows");
-        cap *= 2;
+        cap_override = cap * 2;
         continue;
       }
     }
@@ -304,9 +270,7 @@ int bloom_shift(const torch::Tensor& tab, const c10::optional<torch::Tensor>& bl
   const int64_t cap = tab.size(0) - 1, W = bloom->numel();
   TORCH_CHECK(W <= cap && (W & (W - 1)) == 0 && bloom->is_contiguous() && bloom->scalar_type() == torch::kInt64 &&
                   bloom->device() == tab.device(), "malformed join probe filter");
-  int sh = 0;
-  while ((W << sh) < cap) ++sh;
-  return sh;
+  return nsdb::join_filter_shift(cap, W);
 }
 
 // Probe a built table with m int64 keys: all (build row, probe row) pairs with equal keys, probe-major.
@@ -326,7 +290,7 @@ std::vector<torch::Tensor> join_probe(torch::Tensor tab, torch::Tensor perm, tor
   auto i32 = keys.options().dtype(torch::kInt32);
   auto cnt = torch::empty({m}, i32);
   auto pay = torch::empty({m}, i32);
-  const int64_t tiles = nsdb_join_tiles(m);
+  const int64_t tiles = nsdb::join_tiles(m);
   auto tsum = torch::empty({tiles + 1}, i64);
   const int bsh = bloom_shift(tab, bloom);
   rc_ok(nsdb_join_probe(keys.data_ptr(), m, tab.data_ptr(), cap, reinterpret_cast<unsigned*>(cnt.data_ptr<int>()),
@@ -351,7 +315,7 @@ std::vector<torch::Tensor> join_probe(torch::Tensor tab, torch::Tensor perm, tor
 // Stable partition permutation of dest (values in [0, P)): rows of partition 0 first (input order), then 1, ...
 std::vector<torch::Tensor> partition_perm(torch::Tensor dest, int64_t P) {
   TORCH_CHECK(dest.is_cuda() && dest.scalar_type() == torch::kInt64 && dest.dim() == 1, "dest: 1-D int64 GPU tensor");
-  TORCH_CHECK(P >= 1 && P <= 2048, "partition_perm: 1 <= P <= 2048");
+  TORCH_CHECK(P >= 1 && P <= nsdb::kPartMaxP, "partition_perm: 1 <= P <= ", nsdb::kPartMaxP);
   dest = dest.contiguous();
   const int64_t n = dest.numel();
   TORCH_CHECK(n < (int64_t(1) << 31), "partition_perm: at most 2^31 - 1 rows");
@@ -359,7 +323,7 @@ std::vector<torch::Tensor> partition_perm(torch::Tensor dest, int64_t P) {
   auto counts = torch::zeros({P}, i64);
   auto perm = torch::empty({n}, i64);
   if (n == 0) return {perm, counts};
-  auto work = torch::empty({(nsdb_part_work_bytes(n, (int)P) + 7) / 8}, i64);
+  auto work = torch::empty({(nsdb::part_plan(n, P).total + 7) / 8}, i64);
   rc_ok(nsdb_partition_perm(LL(dest.data_ptr<int64_t>()), n, (int)P, work.data_ptr(), LL(perm.data_ptr<int64_t>()),
                             LL(counts.data_ptr<int64_t>()), stream()),
         "partition_perm");
@@ -381,7 +345,7 @@ torch::Tensor compact(torch::Tensor mask) {
     mask = mask.clone();
     mp = reinterpret_cast<const unsigned char*>(mask.data_ptr());
   }
-  const int64_t T = nsdb_compact_tiles(n);
+  const int64_t T = nsdb::compact_tiles(n);
   auto cnt = torch::empty({T}, mask.options().dtype(torch::kInt32));
   auto off = torch::empty({T + 1}, i64);
   rc_ok(nsdb_compact_count(mp, n, reinterpret_cast<unsigned*>(cnt.data_ptr<int32_t>()), LL(off.data_ptr<int64_t>()),
@@ -429,27 +393,12 @@ std::vector<torch::Tensor> run_aggregate(torch::Tensor keys, c10::optional<torch
   TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == torch::kInt64 && keys.dim() == 1, "keys must be 1-D int64 GPU");
   keys = keys.contiguous();
   const int64_t n = keys.numel();
-  const int opc = op == "sum" ? 0 : op == "min" ? 1 : op == "max" ? 2 : -1;
-  TORCH_CHECK(opc >= 0, "op must be sum, min or max");
-  int F = 0, vt = 0;
-  int64_t vrs = 0, vcs = 0;
-  torch::Tensor v;
-  auto vdtype = torch::kFloat64;
-  if (vals.has_value() && vals->defined() && vals->numel() > 0) {
-    v = *vals;
-    TORCH_CHECK(v.is_cuda() && v.device() == keys.device(), "vals must be on the keys' device");
-    TORCH_CHECK(v.scalar_type() == torch::kFloat64 || v.scalar_type() == torch::kInt64, "vals must be float64 or int64");
-    if (v.dim() == 1) v = v.unsqueeze(1);
-    TORCH_CHECK(v.dim() == 2 && v.size(0) == n, "vals must be [n] or [n, F]");
-    vrs = v.stride(0);
-    vcs = v.stride(1);
-    F = (int)v.size(1);
-    vt = v.scalar_type() == torch::kInt64 ? 1 : 0;
-    vdtype = v.scalar_type();
-  }
+  const int opc = op_code(op);
+  const AggVals a = agg_vals(vals, keys, false);
+  const int F = a.F;
   auto i64 = keys.options().dtype(torch::kInt64);
   if (n == 0) return {};
-  const int64_t T = nsdb_compact_tiles(n);
+  const int64_t T = nsdb::compact_tiles(n);
   auto cnt = torch::empty({T}, keys.options().dtype(torch::kInt32));
   auto off = torch::empty({T + 2}, i64);
   rc_ok(nsdb_run_count(keys.data_ptr(), n, reinterpret_cast<unsigned*>(cnt.data_ptr<int32_t>()),
@@ -458,8 +407,8 @@ std::vector<torch::Tensor> run_aggregate(torch::Tensor keys, c10::optional<torch
   const int64_t G = st[0].item<int64_t>();
   if (st[1].item<int64_t>() != 0) return {};
   auto heads = torch::empty({G}, i64), okey = torch::empty({G}, i64), ocnt = torch::empty({G}, i64);
-  auto oagg = torch::empty({G, F}, keys.options().dtype(vdtype));
-  rc_ok(nsdb_run_reduce(keys.data_ptr(), F ? v.data_ptr() : nullptr, vrs, vcs, F, vt, opc, n, LL(off.data_ptr<int64_t>()),
+  auto oagg = torch::empty({G, F}, keys.options().dtype(a.dtype));
+  rc_ok(nsdb_run_reduce(keys.data_ptr(), a.ptr(), a.vrs, a.vcs, F, a.vt, opc, n, LL(off.data_ptr<int64_t>()),
                         G, LL(heads.data_ptr<int64_t>()), LL(okey.data_ptr<int64_t>()), F ? oagg.data_ptr() : nullptr,
                         LL(ocnt.data_ptr<int64_t>()), stream()), "run_reduce");
   return {okey, oagg, ocnt, heads};
@@ -508,10 +457,38 @@ std::vector<torch::Tensor> take_many(std::vector<torch::Tensor> cols, torch::Ten
       pp = (int)(rowb / ww);
     }
     src.push_back(c.data_ptr()); dst.push_back(o.data_ptr()); nsrc.push_back(c.size(0)); w.push_back(ww); per.push_back(pp);
-    if ((int)src.size() == 48) flush();
+    if ((int)src.size() == nsdb::kTakeCols) flush();
   }
   flush();
   return out;
+}
+
+// The key columns of an ORDER BY: 1..4 one-dimensional int32 / int64 / float32 / float64 GPU columns of equal length,
+// made contiguous in place (keys keeps them alive); dt: dtype codes (sort_plan.h), ds: 1 = descending.
+struct OrderKeys {
+  int m = 0;
+  int64_t n = 0;
+  const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
+  int dt[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
+};
+OrderKeys order_keys(std::vector<torch::Tensor>& keys, const std::vector<bool>& desc, const char* who) {
+  OrderKeys k;
+  k.m = (int)keys.size();
+  TORCH_CHECK(k.m >= 1 && k.m <= 4, who, ": 1 to 4 key columns");
+  TORCH_CHECK((int)desc.size() == k.m, who, ": one direction per key");
+  k.n = keys[0].numel();
+  for (int j = 0; j < k.m; ++j) {
+    auto& c = keys[j];
+    TORCH_CHECK(c.is_cuda() && c.dim() == 1 && c.numel() == k.n && c.device() == keys[0].device(), who,
+                ": keys must be 1-D GPU columns of equal length on one device");
+    const auto t = c.scalar_type();
+    k.dt[j] = t == torch::kInt32 ? 0 : t == torch::kFloat32 ? 1 : t == torch::kInt64 ? 2 : t == torch::kFloat64 ? 3 : -1;
+    TORCH_CHECK(k.dt[j] >= 0, who, ": keys must be int32, int64, float32 or float64");
+    c = c.contiguous();
+    k.ptr[j] = c.data_ptr();
+    k.ds[j] = desc[j] ? 1 : 0;
+  }
+  return k;
 }
 
 // ORDER BY keys[0], keys[1], ... LIMIT k (topk.hip): the int64 row ids of the min(k, n) first rows in final order;
@@ -519,36 +496,22 @@ std::vector<torch::Tensor> take_many(std::vector<torch::Tensor> cols, torch::Ten
 // float32 / float64 GPU columns of equal length n < 2^31 (read in place at their native width), min(k, n) <= 2048.
 // No host read: a linear chain of launches on the current stream, scratch from the caching allocator.
 torch::Tensor order_limit(std::vector<torch::Tensor> keys, std::vector<bool> desc, int64_t k) {
-  const int m = (int)keys.size();
-  TORCH_CHECK(m >= 1 && m <= 4, "order_limit: 1 to 4 key columns");
-  TORCH_CHECK((int)desc.size() == m, "order_limit: one direction per key");
-  const int64_t n = keys[0].numel();
-  const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
-  int dt[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
-  for (int j = 0; j < m; ++j) {
-    auto& c = keys[j];
-    TORCH_CHECK(c.is_cuda() && c.dim() == 1 && c.numel() == n && c.device() == keys[0].device(),
-                "order_limit: keys must be 1-D GPU columns of equal length on one device");
-    const auto t = c.scalar_type();
-    dt[j] = t == torch::kInt32 ? 0 : t == torch::kFloat32 ? 1 : t == torch::kInt64 ? 2 : t == torch::kFloat64 ? 3 : -1;
-    TORCH_CHECK(dt[j] >= 0, "order_limit: keys must be int32, int64, float32 or float64");
-    c = c.contiguous();
-    ptr[j] = c.data_ptr();
-    ds[j] = desc[j] ? 1 : 0;
-  }
+  const OrderKeys ok = order_keys(keys, desc, "order_limit");
+  const int m = ok.m;
+  const int64_t n = ok.n;
   auto i64 = keys[0].options().dtype(torch::kInt64);
   if (n == 0 || k <= 0) return torch::empty({0}, i64);
   TORCH_CHECK(n < (int64_t(1) << 31), "order_limit: at most 2^31 - 1 rows");
   const int64_t k_eff = std::min<int64_t>(k, n);
   TORCH_CHECK(k_eff <= nsdb_order_limit_max_k(), "order_limit: k above ", nsdb_order_limit_max_k());
-  const int64_t sbytes = nsdb_order_limit_state_bytes(dt, m, n);
+  const int64_t sbytes = nsdb_order_limit_state_bytes(ok.dt, m, n);
   TORCH_CHECK(sbytes > 0, "order_limit: bad key set");
   auto i32 = keys[0].options().dtype(torch::kInt32);
   auto state = torch::zeros({(sbytes + 7) / 8}, i64);
   auto lists = torch::empty({2 * n}, i32);
   auto win = torch::empty({k_eff}, i32);
   auto out = torch::empty({k_eff}, i64);
-  rc_ok(nsdb_order_limit(ptr, dt, ds, m, n, k, state.data_ptr(), reinterpret_cast<unsigned*>(lists.data_ptr<int>()),
+  rc_ok(nsdb_order_limit(ok.ptr, ok.dt, ok.ds, m, n, k, state.data_ptr(), reinterpret_cast<unsigned*>(lists.data_ptr<int>()),
                          reinterpret_cast<unsigned*>(win.data_ptr<int>()), LL(out.data_ptr<int64_t>()), stream()),
         "order_limit");
   return out;
@@ -573,39 +536,57 @@ pybind11::dict order_by_plan(std::vector<int64_t> dtypes, int64_t n) {
 // (limit < 0: all). Keys and order as order_limit. No host read: a linear chain of launches on the current stream, every
 // scratch buffer sized by the plan and taken from the caching allocator.
 torch::Tensor order_by(std::vector<torch::Tensor> keys, std::vector<bool> desc, int64_t limit) {
-  const int m = (int)keys.size();
-  TORCH_CHECK(m >= 1 && m <= 4, "order_by: 1 to 4 key columns");
-  TORCH_CHECK((int)desc.size() == m, "order_by: one direction per key");
-  const int64_t n = keys[0].numel();
-  const void* ptr[4] = {nullptr, nullptr, nullptr, nullptr};
-  int dt[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0};
-  for (int j = 0; j < m; ++j) {
-    auto& c = keys[j];
-    TORCH_CHECK(c.is_cuda() && c.dim() == 1 && c.numel() == n && c.device() == keys[0].device(),
-                "order_by: keys must be 1-D GPU columns of equal length on one device");
-    const auto t = c.scalar_type();
-    dt[j] = t == torch::kInt32 ? 0 : t == torch::kFloat32 ? 1 : t == torch::kInt64 ? 2 : t == torch::kFloat64 ? 3 : -1;
-    TORCH_CHECK(dt[j] >= 0, "order_by: keys must be int32, int64, float32 or float64");
-    c = c.contiguous();
-    ptr[j] = c.data_ptr();
-    ds[j] = desc[j] ? 1 : 0;
-  }
+  const OrderKeys ok = order_keys(keys, desc, "order_by");
+  const int m = ok.m;
+  const int64_t n = ok.n;
   auto i64 = keys[0].options().dtype(torch::kInt64);
   if (n == 0 || limit == 0) return torch::empty({0}, i64);
   TORCH_CHECK(n < (int64_t(1) << 31), "order_by: at most 2^31 - 1 rows");
   const int64_t lim = limit < 0 ? n : std::min<int64_t>(limit, n);
   long long f[12];
-  TORCH_CHECK(nsdb_order_by_plan(dt, m, n, f) == 0, "order_by: bad key set (plan code ", f[0], ")");
+  TORCH_CHECK(nsdb_order_by_plan(ok.dt, m, n, f) == 0, "order_by: bad key set (plan code ", f[0], ")");
   const int64_t state_b = f[7], counts_b = f[8], words_b = f[9], ids_b = f[10];
   auto state = torch::zeros({(state_b + 7) / 8}, i64);
   auto counts = torch::empty({(counts_b + 7) / 8}, i64);
   auto words = torch::empty({(words_b + 7) / 8}, i64);
   auto ids = torch::empty({(ids_b + 7) / 8}, i64);
   auto out = torch::empty({lim}, i64);
-  rc_ok(nsdb_order_by(ptr, dt, ds, m, n, lim, state.data_ptr(), counts.data_ptr(), words.data_ptr(), ids.data_ptr(),
+  rc_ok(nsdb_order_by(ok.ptr, ok.dt, ok.ds, m, n, lim, state.data_ptr(), counts.data_ptr(), words.data_ptr(), ids.data_ptr(),
                       LL(out.data_ptr<int64_t>()), stream()),
         "order_by");
   return out;
+}
+
+// The plan of hash_aggregate for n rows and F value columns under the current MID setting (relops_plan.h agg_plan);
+// launches nothing. scratch_low / scratch_part: status[4] of a call that ends on the LOW (or MID) / the PART path.
+pybind11::dict hash_aggregate_plan(int64_t n, int64_t F, int64_t low_threshold, bool want_inv, bool want_first) {
+  const nsdb::AggPlan p = nsdb::agg_plan(n, (int)F, low_threshold, g_agg_mid, want_inv, want_first);
+  pybind11::dict d;
+  d["rc"] = p.rc;
+  if (p.rc != nsdb::AGG_OK) return d;
+  const std::pair<const char*, int64_t> f[] = {
+      {"lcap_low", p.lcap_low}, {"lcap_part", p.lcap_part}, {"lcap_mid", p.lcap_mid}, {"gcap_low", p.glow.cap},
+      {"gcap_part", p.gpart.cap}, {"low_thr", p.low_thr}, {"pbits", p.pbits}, {"P", p.P}, {"G", p.G}, {"rpw", p.rpw},
+      {"T", p.T}, {"T2", p.T2}, {"ocap_low", p.ocap_low}, {"table_words_low", p.glow.words},
+      {"table_words_part", p.gpart.words}, {"work_bytes", p.work.total}, {"phase1_bytes", p.phase1_bytes},
+      {"part_bytes", p.part_bytes}, {"scratch_low", p.phase1_bytes},
+      {"scratch_part", p.phase1_bytes + p.part_bytes - 8 * nsdb::agg_out(p.ocap_low, p.F).words}};
+  for (const auto& kv : f) d[kv.first] = kv.second;
+  return d;
+}
+
+// The plan of join_build for n build rows under the current filter / partition settings (relops_plan.h join_plan);
+// launches nothing. bloom_words and stat_words are the sizes of join_build's third and fourth tensors.
+pybind11::dict join_build_plan(int64_t n) {
+  const nsdb::JoinPlan p = join_plan_now(n, 0);
+  pybind11::dict d;
+  const std::pair<const char*, int64_t> f[] = {
+      {"load", p.load}, {"cap", p.cap}, {"regions", p.regions}, {"part", p.part}, {"bloom_words", p.W},
+      {"bshift", p.bshift}, {"fold", p.fold}, {"stat_words", p.regions ? 2 : 0}, {"rc", p.part ? p.work.rc : 0},
+      {"P", p.work.P}, {"G", p.work.G}, {"Pc", p.work.Pc}, {"sh", p.work.sh}, {"rpw", p.work.rpw},
+      {"work_bytes", p.work.total}};
+  for (const auto& kv : f) d[kv.first] = kv.second;
+  return d;
 }
 }  // namespace
 
@@ -620,6 +601,12 @@ void register_relops(pybind11::module& m) {
         pybind11::arg("keys"), pybind11::arg("vals") = pybind11::none(), pybind11::arg("op") = "sum",
         pybind11::arg("want_inv") = false, pybind11::arg("low_threshold") = 0, pybind11::arg("want_first") = true,
         pybind11::arg("scratch") = pybind11::none());
+  m.def("hash_aggregate_plan", &hash_aggregate_plan, "plan of hash_aggregate for n rows and F value columns: table "
+        "capacities, PART geometry and the scratch bytes of either path; launches nothing", pybind11::arg("n"),
+        pybind11::arg("F"), pybind11::arg("low_threshold") = 0, pybind11::arg("want_inv") = false,
+        pybind11::arg("want_first") = true);
+  m.def("join_build_plan", &join_build_plan, "plan of join_build for n build rows: load factor, slots, table kind, "
+        "probe filter and partition geometry; launches nothing", pybind11::arg("n"));
   m.def("take_many", &take_many, "rows idx of several device columns in one launch (bad: int32 device word set on "
         "an out-of-range id)", pybind11::arg("cols"), pybind11::arg("idx"), pybind11::arg("bad"));
   m.def("join_build", &join_build, "device hash-join build: (table, perm, probe filter (empty: none), host [fail, "

@@ -782,12 +782,18 @@ def test_join_region_overflow_rebuilds_larger():
 
 
 def test_join_region_constants_agree():
-    """relops.hip and pipeline_core.h (the fused probes) must walk the same probe order."""
+    """relops_plan.h (the join build and probe of relops.hip) and pipeline_core.h (the fused probes) must walk the same
+    probe order; pipeline.hip, which sees both, asserts it at compile time."""
     import re
     from pathlib import Path
 
     kd = Path(__file__).resolve().parents[1] / "netsdb_amd" / "csrc" / "kernels"
-    r = (kd / "relops.hip").read_text()
+    r = (kd / "relops_plan.h").read_text()
     c = (kd / "pipeline_core.h").read_text()
-    assert re.search(r"constexpr int kJRegionBits = 12;", r) and "constexpr u64 kJWholeWrap = 1ull << 22;" in r
+    assert re.search(r"constexpr int kJRegionBits = 12;", r)
+    assert "constexpr unsigned long long kJRegion = 1ull << kJRegionBits;" in r
+    assert "constexpr unsigned long long kJWholeWrap = 1ull << 22;" in r
     assert "constexpr unsigned long long JREGION = 4096, JWHOLE = 1ull << 22;" in c
+    assert "static_assert(nsdb_pipe::JREGION == nsdb::kJRegion && nsdb_pipe::JWHOLE == nsdb::kJWholeWrap" in \
+        (kd / "pipeline.hip").read_text()
+    assert "kJRegionBits =" not in (kd / "relops.hip").read_text()      # one definition, in the plan
