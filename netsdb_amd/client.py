@@ -428,6 +428,23 @@ class PDBClient:
 
     exportSet = export_set
 
+    def load_delimited(self, db: str, name: str, path: str, **kw) -> dict:
+        """Ingest a delimited-text file (``.tbl``, CSV without quoting) into an existing typed set, parsed on this
+        client's device (storage/textload.py load_delimited: delimiter, trailing, header, fields, dates,
+        chunk_bytes, policy). Returns {rows, bytes, seconds, chunks, host_cells}."""
+        from .storage import textload
+
+        return textload.load_delimited(self, db, name, path, **kw)
+
+    def import_set(self, db: str, name: str, path: str, fmt: str = "csv") -> dict:
+        """The inverse of :meth:`export_set`: read back a CSV it wrote (header line of field names) into the
+        existing set ``db.name``."""
+        from .storage import textload
+
+        return textload.import_set(self, db, name, path, fmt)
+
+    importSet = import_set
+
     def register_node(self, address: str, port: int = 0, name: str = "", node_type: str = "worker",
                       status: int = 0) -> bool:
         self.catalog.register_node(self.ctx.rank, f"{address}:{port}", name or node_type, 0)

@@ -83,6 +83,7 @@ int nsdb_str_cmp_pairs(const void* a, const int64_t* sta, const int64_t* ena, co
 
 void register_relops(pybind11::module& m);
 void register_pipeline(pybind11::module& m);
+void register_textparse(pybind11::module& m);
 std::vector<torch::Tensor> hash_aggregate_impl(torch::Tensor keys, c10::optional<torch::Tensor> vals,
                                                const std::string& op, bool want_inv, int64_t low_threshold);
 
@@ -940,6 +941,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "netsdb_amd CDNA4 (gfx950) HIP kernels";
   register_relops(m);
   register_pipeline(m);
+  register_textparse(m);
   m.def("gemm_nt", &gemm_nt, "epi(alpha*A@B^T) on MFMA", py::arg("A"), py::arg("B"), py::arg("bias") = py::none(),
         py::arg("bias_mode") = 0, py::arg("act") = 0, py::arg("out_f32") = false, py::arg("alpha") = 1.0,
         py::arg("dropout") = 0.0, py::arg("seed") = 0, py::arg("splits") = 0, py::arg("out") = py::none(),

@@ -129,11 +129,29 @@ def _parse_numeric(buf: torch.Tensor, s: torch.Tensor, e: torch.Tensor, as_float
     return val.to(torch.float64) / p10[frac].to(torch.float64)
 
 
-def parse_tbl(buf: torch.Tensor, table: str, device=None) -> RecordBatch:
+def parse_tbl(buf: torch.Tensor, table: str, device=None, path: Optional[str] = None) -> RecordBatch:
     """One chunk of whole ``.tbl`` lines (uint8 tensor) -> a RecordBatch of ``table``'s schema (numbers as int64 /
     float64 tensors, dates as int yyyymmdd, text as StringColumns on the chunk's device, or host lists on a CPU
-    device when device strings are off)."""
+    device when device strings are off).
+
+    ``path="torch"`` is the whole-column tensor parser below; ``path="device"`` maps the table's schema onto the
+    delimited-text kernels (storage/textload.py parse_delimited; a GPU buffer only). ``None`` takes the kernels for a
+    GPU buffer and the tensor parser for a CPU one: at SF 1 the kernels load 1.05 GB in 0.24 .. 0.28 s against
+    0.49 .. 0.55 s, five interleaved runs each, the ranges apart (profiles/textparse).
+    The two agree bit for bit on dbgen output. The one known difference cannot occur there: the torch parser applies
+    the sign to the integer mantissa, so it reads ``-0.00`` as ``+0.0`` where the kernels (and Python) give ``-0.0``;
+    dbgen writes no negative zero."""
     typ = T.TABLES[table]
+    path = path or ("device" if buf.is_cuda else "torch")
+    if path == "device":
+        from ..storage.textload import parse_delimited
+
+        b = parse_delimited(buf, typ, delimiter="|", trailing=True, path="device")
+        if not use_device_strings(device or buf.device):
+            b.columns = {k: (v.tolist() if isinstance(v, StringColumn) else v) for k, v in b.columns.items()}
+        return b
+    if path != "torch":
+        raise ValueError(f"path must be 'torch' or 'device', got {path!r}")
     fields = list(typ.fields().items())
     starts, ends = _field_bounds(buf, len(fields))
     n = starts.shape[0]
@@ -187,20 +205,21 @@ def read_chunk(path: str, lo: int, hi: int) -> np.ndarray:
 
 
 def load_tbl(client, db: str, tbl_dir: str, device=None, only: Optional[Sequence[str]] = None,
-             chunk_bytes: int = 256 << 20) -> Dict[str, dict]:
+             chunk_bytes: int = 256 << 20, path: Optional[str] = None) -> Dict[str, dict]:
     """Create the TPC-H sets of ``db`` and ingest ``<tbl_dir>/<table>.tbl`` (tpchDataLoader.cc). Rank 0 reads and
     parses each chunk on ``device`` (default: the client's) and dispatches it by the set's partition policy
-    (send_data: a collective, so every rank takes part chunk by chunk). Returns per-table {rows, bytes, seconds}."""
+    (send_data: a collective, so every rank takes part chunk by chunk). ``path`` picks the parser (parse_tbl). Returns
+    per-table {rows, bytes, seconds}."""
     dev = torch.device(device) if device is not None else client.device
     client.create_database(db)
     stats = {}
     for name, typ in T.TABLES.items():
         if only is not None and name not in only:
             continue
-        path = os.path.join(tbl_dir, f"{name}.tbl")
+        fpath = os.path.join(tbl_dir, f"{name}.tbl")
         client.create_set(db, name, typ)
         t0 = time.perf_counter()
-        bounds = chunk_bounds(path, chunk_bytes) if client.ctx.rank == 0 else None
+        bounds = chunk_bounds(fpath, chunk_bytes) if client.ctx.rank == 0 else None
         nchunks = len(bounds) if bounds is not None else 0
         if client.ctx.distributed:
             nchunks = int(client.ctx.all_reduce_scalar(float(nchunks), "max"))
@@ -208,12 +227,12 @@ def load_tbl(client, db: str, tbl_dir: str, device=None, only: Optional[Sequence
         for i in range(nchunks):
             b = None
             if client.ctx.rank == 0:
-                seg = read_chunk(path, *bounds[i])
+                seg = read_chunk(fpath, *bounds[i])
                 host = torch.from_numpy(seg)
                 if dev.type == "cuda":
                     host = host.pin_memory()
                 buf = host.to(dev, non_blocking=True)
-                b = parse_tbl(buf, name, dev)
+                b = parse_tbl(buf, name, dev, path)
                 del buf
                 rows += b.n
                 nbytes += seg.size

@@ -21,7 +21,8 @@ RDIR = os.path.join("netsdb_amd", "csrc", "runtime")
 
 
 HIP_SOURCES = ("gemm.hip", "gemm_f32.hip", "conv2d.hip", "rowops.hip", "strings.hip", "dedup.hip", "relops.hip",
-               "topk.hip", "sort.hip", "relops_bind.cpp", "pipeline.hip", "pipeline_bind.cpp")
+               "topk.hip", "sort.hip", "relops_bind.cpp", "pipeline.hip", "pipeline_bind.cpp", "textparse.hip",
+               "textparse_bind.cpp")
 PER_FILE_FLAGS = {}          # per-source extra hipcc flags
 SDIR = os.path.join("netsdb_amd", "csrc", "study")
 STUDY_SOURCES = ("gemm_study.hip",)
